@@ -8,6 +8,18 @@ collective (weak scaling: envs per GPU fixed); each rank times K steps between a
 device sync, rank 0 reports the max over ranks.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C3|C4|C5] [--obs flat|native]
+                  [--full] [--dump-outputs DIR]
+
+A plain run does what the headline figure needs: it builds and staggers the envs, warms up, times
+the K steps and prints the line (`value`, `ms_per_step` = the wall milliseconds of one timed step).
+`--full` adds everything else described below: `kernel_ms` and `roofline` (eager and policy-only
+runs after the timed steps), `extra_configs`, `cpu_baseline`, and for C5 the stored / decoded
+passes, the node model and the one-GPU reference; without it those fields are null.
+`--dump-outputs DIR` writes what the last timed step left for its caller as DIR/<name>.npy
+(float32): reward, terminated, truncated, mask [envs, agents] in full and `obs_sample`, a fixed
+seeded sample of the obs rows (C5: `wire_sample_batch<j>`, of each batch's wire buffer bytes; C2
+and C3 have no obs). Inputs are generated from
+`--seed`, so two builds run with the same arguments compare array for array.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts N ranks itself (a child
 `torch.distributed.run --nproc-per-node N`, before anything touches the GPU) and exits with its
@@ -174,9 +186,17 @@ def parse(argv=None):
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--stagger", type=int, default=64,
                     help="pre-roll ticks over which env episode phases are staggered (0 = lockstep)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure also measure everything else the line can carry: the CPU "
+                         "baseline, the extra_configs, kernel_ms and roofline (runs of their own after the timed "
+                         "steps), C5's stored / decoded passes, node model and one-GPU reference. Without it a run "
+                         "sets up, warms up, times --steps steps and prints the line, those fields null")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path's last step left for its caller as "
+                         "DIR/<name>.npy (float32; a fixed, seeded sample of the large obs buffer)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra_configs at N = 1")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the extra_configs")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
     ap.add_argument("--graph-steps", type=int, default=10, help="ticks captured per hipGraph")
     ap.add_argument("--batches", type=int, default=2,
@@ -394,7 +414,76 @@ def _progress(msg: str) -> None:
         print(f"bench.py [{time.perf_counter() - _T0:7.1f} s] {msg}", file=sys.stderr, flush=True)
 
 
-def measure(args, name, layout_name, envs, rank, world, dev, steps, warmup, dist=None, wrapper=None):
+DUMP_SEED = 20231101
+DUMP_SAMPLE_BYTES = 40 << 20  # float32 bytes of the obs sample; with the per-agent outputs well under 64 MB
+
+
+def _sample_rows(mats, seed=DUMP_SEED, budget=DUMP_SAMPLE_BYTES):
+    """A fixed sample of the rows of the 2-D device tensors `mats` stacked (equal columns): as many
+    rows as `budget` bytes of float32 hold, drawn once from Generator(seed) over the stacked row
+    index and taken in ascending order; every row when they all fit. float32 numpy [k, columns]."""
+    import numpy as np
+    import torch
+
+    counts = [m.shape[0] for m in mats]
+    total, cols = sum(counts), mats[0].shape[1]
+    k = max(1, min(total, budget // (4 * cols)))
+    idx = np.arange(total) if k == total else np.sort(np.random.default_rng(seed).choice(total, k, replace=False))
+    out, lo = [], 0
+    for m, c in zip(mats, counts):
+        sel = idx[(idx >= lo) & (idx < lo + c)] - lo
+        if sel.size:
+            out.append(m[torch.from_numpy(sel).to(m.device)].to(torch.float32).cpu().numpy())
+        lo += c
+    return np.concatenate(out)
+
+
+def _write_outputs(out_dir, arrays):
+    """--dump-outputs: each array as out_dir/<name>.npy, float32."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for nm, a in arrays.items():
+        np.save(os.path.join(out_dir, nm + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    _progress(f"wrote {', '.join(sorted(arrays))} to {out_dir}")
+
+
+def _engine_outputs(engs, has_obs):
+    """What step() of the engines (consecutive env blocks) last returned to its caller: reward,
+    terminated, truncated and mask [envs, P] in full, and of the obs buffer (flat: a row per agent;
+    native: a row per env) the fixed row sample of _sample_rows."""
+    import torch
+
+    def whole(field):
+        return torch.cat([getattr(e, field) for e in engs]).to(torch.float32).cpu().numpy()
+
+    out = {"reward": whole("rew"), "terminated": whole("term"), "truncated": whole("trunc"), "mask": whole("mask")}
+    if has_obs:
+        out["obs_sample"] = _sample_rows([e.obs.view(-1, e.obs.shape[-1]) for e in engs])
+    return out
+
+
+def _wire_outputs(g):
+    """What WireGather g's last step left for the learner from this rank's batches: reward,
+    terminated, truncated and mask [envs, P] from the step records, and of each batch's wire buffer
+    (header + records, its announced bytes) the fixed sample of _sample_rows over its bytes."""
+    import numpy as np
+
+    from nmmo_amd import wire as nw
+
+    k = (g.t - 1) % g.ring
+    rec = np.concatenate([g.smalls[j][k].cpu().numpy() for j in range(len(g.engines))])  # [envs, P, 8]
+    out = {"reward": np.ascontiguousarray(rec[..., :4]).view(np.float32)[..., 0],
+           "terminated": rec[..., 4], "truncated": rec[..., 5], "mask": rec[..., 6]}
+    nb = len(g.engines)
+    for j in range(nb):
+        w = g.wires[j][k]
+        out[f"wire_sample_batch{j}"] = _sample_rows([w[:nw.total_bytes(w)].view(-1, 1)],
+                                                    budget=DUMP_SAMPLE_BYTES // nb)[:, 0]
+    return out
+
+
+def measure(args, name, layout_name, envs, rank, world, dev, steps, warmup, dist=None, wrapper=None, dump=None):
     """Build, stagger, warm up and time one gather-free workload on this rank; returns a result
     dict.
 
@@ -509,6 +598,39 @@ def measure(args, name, layout_name, envs, rank, world, dev, steps, warmup, dist
     rows_written, bytes_stored = float(obs_cnt[0].item()), float(obs_cnt[1].item())
     events_per_env_tick = float(tot[2].item()) / (envs * steps) if cfg.event_cap > 0 else None
     _progress(f"{name}: timed {steps} steps in {elapsed:.3f} s")
+    if dump and rank == 0:
+        _write_outputs(dump, _engine_outputs(engs, wl["obs"]))
+    prof_name = name + ("-native" if native else "-rezero" if rezero else "-tilewriter" if tile_writer else "") + \
+        ("" if wrapper == "none" else "+" + wrapper)
+    launch = "eager" if not plans else f"hipGraph x{min(args.graph_steps, steps)} ticks"
+    if nb > 1:
+        launch += f", {nb} batches of {per} envs on {nb} streams"
+    S, P = eng.S, cfg.PLAYER_N
+    row_frac = rows_written / (envs * P * steps)  # the timed steps' rows written per agent row
+    res = {
+        "name": prof_name, "envs": envs, "cfg": cfg, "layout": "native" if native else "flat", "S": S, "P": P,
+        "elapsed": elapsed, "alive": alive, "slots": float(envs * P * steps), "episodes": episodes,
+        "events_per_env_tick": events_per_env_tick, "gather": False, "launch": launch, "wrapper": wrapper,
+        "kernel_ms": None, "roofline": None,  # --full: runs of their own, below
+        "batches": nb,
+        "obs_contract": None if not wl["obs"] else
+        ("every row written in full each step (GpuVecEnv obs_writes=\"all\": a consumer that may edit any "
+         "section in place)" if rezero else
+         "incremental rows with every Tile section rewritten each step (GpuVecEnv obs_writes={\"Tile\"}, the "
+         "start-kit agent's default: its TileEncoder edits Tile[:, :, :2] in place)" if tile_writer else
+         "incremental rows into the engine's bound buffer: a row stores only what differs from what the buffer "
+         "holds (DESIGN.md §3.2c); valid for a read-only consumer (GpuVecEnv obs_writes=set(): the takeru and "
+         "yaofeng agents' default)"),
+        "obs_rows_written_frac": round(row_frac, 4) if wl["obs"] else None,
+        "obs_bytes_stored_per_agent_row": round(bytes_stored / (envs * P * steps), 1) if wl["obs"] else None,
+    }
+    if not args.full:
+        _check_faults(args, engs, name, world, dist, dev)  # every tick of this workload ran
+        for e in engs:
+            e.close()
+        del eng, engs
+        torch.cuda.empty_cache()
+        return res
     tick_avg_ms, obs_avg_ms, wrap_avg_ms = _kernel_timing(eng, pseed, steps)
     # The roofline's tick duration without per-kernel event overhead (which inflates a ~15 us
     # launch by ~20%): the timed step (policy + nmmo_step, graph-replayed) minus a hipGraph of
@@ -544,10 +666,8 @@ def measure(args, name, layout_name, envs, rank, world, dev, steps, warmup, dist
         solo_step_ms = b0.elapsed_time(b1) / (reps * batch)
     fill_gbs = _write_ceiling(eng.obs, dev) if wl["obs"] else None
 
-    S, P = eng.S, cfg.PLAYER_N
     slim = not any(x in cfg.systems for x in ("Item", "Equipment", "Profession", "Exchange"))
     tick_b = tick_bytes_per_env(S, P, "Item" in cfg.systems, events_per_env_tick or 0.0, slim) * per
-    row_frac = rows_written / (envs * P * steps)  # the timed steps' rows written per agent row
     obs_b = obs_bytes_per_env(S, P, eng.obs_elems, native, stored=bytes_stored / (envs * steps),
                               alive_frac=alive / (envs * P * steps)) * per if wl["obs"] else 0
     if wl["obs"] and obs_avg_ms > tick_avg_ms:
@@ -571,33 +691,12 @@ def measure(args, name, layout_name, envs, rank, world, dev, steps, warmup, dist
     full_b = None  # §8(d)'s model: every row written in full
     if wl["obs"] and kern != "tick_kernel" and not rezero:
         full_b = obs_bytes_per_env(S, P, eng.obs_elems, native, alive_frac=alive / (envs * P * steps)) * per
-    prof_name = name + ("-native" if native else "-rezero" if rezero else "-tilewriter" if tile_writer else "") + \
-        ("" if wrapper == "none" else "+" + wrapper)
-    launch = "eager" if not plans else f"hipGraph x{min(args.graph_steps, steps)} ticks"
-    if nb > 1:
-        launch += f", {nb} batches of {per} envs on {nb} streams"
-    res = {
-        "name": prof_name, "envs": envs, "cfg": cfg, "layout": "native" if native else "flat", "S": S, "P": P,
-        "elapsed": elapsed, "alive": alive, "slots": float(envs * P * steps), "episodes": episodes,
-        "events_per_env_tick": events_per_env_tick, "gather": False, "launch": launch, "wrapper": wrapper,
-        "kernel_ms": {"policy": round(policy_avg_ms, 5), "tick": round(tick_avg_ms, 5),
-                      "obs": round(obs_avg_ms, 5) if wl["obs"] else None,
-                      "wrapper": round(wrap_avg_ms, 5) if wrapper != "none" else None},
-        "roofline": _roofline(prof_name, kern, byts, ms, per, timing, nb, elapsed / steps, fill_gbs, full_b=full_b,
-                              byte_model=None if not wl["obs"] or kern == "tick_kernel" else
-                              "full rows" if rezero else "stored bytes"),
-        "batches": nb,
-        "obs_contract": None if not wl["obs"] else
-        ("every row written in full each step (GpuVecEnv obs_writes=\"all\": a consumer that may edit any "
-         "section in place)" if rezero else
-         "incremental rows with every Tile section rewritten each step (GpuVecEnv obs_writes={\"Tile\"}, the "
-         "start-kit agent's default: its TileEncoder edits Tile[:, :, :2] in place)" if tile_writer else
-         "incremental rows into the engine's bound buffer: a row stores only what differs from what the buffer "
-         "holds (DESIGN.md §3.2c); valid for a read-only consumer (GpuVecEnv obs_writes=set(): the takeru and "
-         "yaofeng agents' default)"),
-        "obs_rows_written_frac": round(row_frac, 4) if wl["obs"] else None,
-        "obs_bytes_stored_per_agent_row": round(bytes_stored / (envs * P * steps), 1) if wl["obs"] else None,
-    }
+    res["kernel_ms"] = {"policy": round(policy_avg_ms, 5), "tick": round(tick_avg_ms, 5),
+                        "obs": round(obs_avg_ms, 5) if wl["obs"] else None,
+                        "wrapper": round(wrap_avg_ms, 5) if wrapper != "none" else None}
+    res["roofline"] = _roofline(prof_name, kern, byts, ms, per, timing, nb, elapsed / steps, fill_gbs, full_b=full_b,
+                                byte_model=None if not wl["obs"] or kern == "tick_kernel" else
+                                "full rows" if rezero else "stored bytes")
     _check_faults(args, engs, name, world, dist, dev)  # every tick of this workload ran (timed and after)
     for e in engs:
         e.close()
@@ -715,7 +814,7 @@ def _record_store(per_list, dev, P):
 
 
 def measure_gather(args, name, envs, rank, world, dev, steps, warmup, dist=None, backend="nccl", shares=None,
-                   modes=None):
+                   modes=None, dump=None):
     """C5: the rank's envs (its share of the node) as `--batches` wire-obs handles stepped by
     WireGather (policy + nmmo_step into a ring of wire buffers, hipGraph-captured, one stream per
     batch; the learner gather into rank 0 one step behind on a comm stream). Timed passes over
@@ -744,6 +843,8 @@ def measure_gather(args, name, envs, rank, world, dev, steps, warmup, dist=None,
         e.set_counters(c)
     torch.cuda.synchronize(dev)
     passes = {}
+    if not args.full:
+        modes = ("delivered",)  # the headline pass alone
     modes = modes or (("delivered",) if args.no_decode else ("delivered", "stored", "decoded"))
     for mode in modes:
         store = None
@@ -753,10 +854,14 @@ def measure_gather(args, name, envs, rank, world, dev, steps, warmup, dist=None,
                        backend=backend, store=store)
         passes[mode] = _gather_pass(args, engs, g, steps, warmup, world, dist, dev, counters, store)
         _progress(f"{name}: timed {steps} steps in {passes[mode]['elapsed']:.3f} s ({mode})")
+        if dump and rank == 0 and mode == "delivered":
+            _write_outputs(dump, _wire_outputs(g))
         g.close()
         del store
     eng = engs[0]
-    tick_avg_ms, obs_avg_ms, _ = _kernel_timing(eng, pseed, steps)
+    kernel_ms = roofline = None
+    if args.full:  # runs of their own after the timed passes
+        tick_avg_ms, obs_avg_ms, _ = _kernel_timing(eng, pseed, steps)
     _check_faults(args, engs, name, world, dist, dev)
     from nmmo_amd import wire as nw
 
@@ -764,25 +869,28 @@ def measure_gather(args, name, envs, rank, world, dev, steps, warmup, dist=None,
     S, P = eng.S, cfg.PLAYER_N
     d = passes["delivered"]
     events_per_env_tick = d["events"] / (envs * steps)
-    tick_b = tick_bytes_per_env(S, P, True, events_per_env_tick) * per
-    obs_b = obs_bytes_per_env(S, P, eng.obs_elems, wire_bytes=wire_env_bytes) * per
-    if obs_avg_ms > tick_avg_ms:
-        kern, byts, ms = "wire_obs_kernel", obs_b, obs_avg_ms
-        timing = ("HIP events around each wire obs gather (wire_scan + wire_obs_kernel; the count words come "
-                  "from the tick, tick.hip wire_count_fused) on the launch stream")
-    else:
-        kern, byts, ms = "tick_kernel", tick_b, tick_avg_ms
-        timing = "HIP events around each tick_kernel launch on the launch stream"
+    if args.full:
+        tick_b = tick_bytes_per_env(S, P, True, events_per_env_tick) * per
+        obs_b = obs_bytes_per_env(S, P, eng.obs_elems, wire_bytes=wire_env_bytes) * per
+        if obs_avg_ms > tick_avg_ms:
+            kern, byts, ms = "wire_obs_kernel", obs_b, obs_avg_ms
+            timing = ("HIP events around each wire obs gather (wire_scan + wire_obs_kernel; the count words come "
+                      "from the tick, tick.hip wire_count_fused) on the launch stream")
+        else:
+            kern, byts, ms = "tick_kernel", tick_b, tick_avg_ms
+            timing = "HIP events around each tick_kernel launch on the launch stream"
+        kernel_ms = {"policy": None, "tick": round(tick_avg_ms, 5), "obs": round(obs_avg_ms, 5), "wrapper": None}
+        roofline = _roofline(name, kern, byts, ms, per, timing, nb, d["elapsed"] / steps, None,
+                             ["wire_count_kernel?", "wire_scan_kernel", "wire_obs_kernel"] if kern == "wire_obs_kernel"
+                             else None)
     res = {
         "name": name, "envs": envs, "cfg": cfg, "layout": "wire", "S": S, "P": P,
         "elapsed": d["elapsed"], "alive": d["alive"], "slots": float(envs * P * steps), "episodes": d["episodes"],
         "events_per_env_tick": events_per_env_tick, "gather": True, "wrapper": "none",
         "launch": f"hipGraph per step and ring slot, {nb} batches of {per} envs on {nb} streams, gather on a "
                   f"comm stream one step behind",
-        "kernel_ms": {"policy": None, "tick": round(tick_avg_ms, 5), "obs": round(obs_avg_ms, 5), "wrapper": None},
-        "roofline": _roofline(name, kern, byts, ms, per, timing, nb, d["elapsed"] / steps, None,
-                              ["wire_count_kernel?", "wire_scan_kernel", "wire_obs_kernel"] if kern == "wire_obs_kernel"
-                              else None),
+        "kernel_ms": kernel_ms,
+        "roofline": roofline,
         "batches": nb,
         "shares": list(shares),
         "gather_bytes": d["payload_bytes_per_step"] if world > 1 else 0,
@@ -1004,15 +1112,16 @@ def main():
     wl = WORKLOADS[name]
     envs = args.envs or wl["envs"]
 
-    def run(nm, lay, wrapper, n_envs, steps, warmup):
+    def run(nm, lay, wrapper, n_envs, steps, warmup, dump=None):
         t0 = time.perf_counter()
         if WORKLOADS[nm].get("gather"):
             shares = c5_shares(args, world, max(1, args.batches))
-            r = measure_gather(args, nm, n_envs, rank, world, dev, steps, warmup, dist, backend, shares=shares)
-            if world == 1 and args.root_rehearsal > 1 and args.envs is None:
+            r = measure_gather(args, nm, n_envs, rank, world, dev, steps, warmup, dist, backend, shares=shares,
+                               dump=dump)
+            if args.full and world == 1 and args.root_rehearsal > 1 and args.envs is None:
                 r["n_model"] = measure_root_model(args, dev, steps, warmup, args.root_rehearsal)
         else:
-            r = measure(args, nm, lay, n_envs, rank, world, dev, steps, warmup, dist, wrapper)
+            r = measure(args, nm, lay, n_envs, rank, world, dev, steps, warmup, dist, wrapper, dump=dump)
         _progress(f"{r['name']} measured in {time.perf_counter() - t0:.1f} s")
         return r
 
@@ -1045,11 +1154,11 @@ def main():
                 out[mode]["rows_stored_per_sec"] = round(r[mode]["stored_rows"] / el, 1)
         return out
 
-    res = run(name, args.obs, None, envs, args.steps, args.warmup)
+    res = run(name, args.obs, None, envs, args.steps, args.warmup, dump=args.dump_outputs)
     elapsed, alive_total, slots_total = reduce(res)
     passes = learner_passes(res, args.steps) if res.get("gather") else {}
     one_gpu = None
-    if res.get("gather") and world > 1 and not args.no_c5_reference:
+    if args.full and res.get("gather") and world > 1 and not args.no_c5_reference:
         # the like-for-like scaling base: C5 at N = 1 (1024 envs, the root's own buffers in place,
         # nothing sent) on rank 0's GPU in this run, while the other ranks wait
         if rank == 0:
@@ -1063,7 +1172,7 @@ def main():
         dist.barrier()
 
     extras = {}
-    if not args.no_extras and not args.envs and args.config is None:
+    if args.full and not args.no_extras and not args.envs and args.config is None:
         ex_steps, ex_warm = max(args.steps, 100), max(args.warmup, 20)
         for nm, lay, wrapper in (EXTRAS if world == 1 else EXTRAS_MULTI):
             r = run(nm, lay, wrapper, WORKLOADS[nm]["envs"], ex_steps, ex_warm)
@@ -1079,7 +1188,7 @@ def main():
 
     if rank == 0:
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             from nmmo_amd import abi
             from nmmo_amd.config import Config
 

@@ -1,6 +1,6 @@
 #!/bin/bash
-# Collects the rocprofv3 summaries committed under profiles/<tag>/ (run on the GPU box via
-# gpurun; outputs go to gpurun_out/prof_<tag>/, which gpurun merges back).
+# Collects the rocprofv3 summaries committed under profiles/<tag>/ (run on the GPU box;
+# outputs go to bench_out/prof_<tag>/).
 #   per config: kernel trace + stats, then FETCH_SIZE and WRITE_SIZE in separate --pmc passes
 #   (MI355X_MICROARCH.md: TCC slots: FETCH_SIZE costs 3, WRITE_SIZE 2 -> one per pass), and a
 #   JSON summary (tools/pmc_summary.py) that bench.py reads for roofline.traffic.
@@ -10,7 +10,7 @@ TAG=${1:-r01}; shift || true
 CONFIGS=${@:-C2 C3 C4 C4-native storage}
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
-OUT=gpurun_out/prof_$TAG
+OUT=bench_out/prof_$TAG
 mkdir -p $OUT
 for c in $CONFIGS; do
   mkdir -p $OUT/$c
@@ -35,11 +35,11 @@ for c in $CONFIGS; do
     continue
   fi
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$c/trace -o run -- \
-    python3 bench.py $ARGS --steps 100 --warmup 20 --no-cpu-baseline --no-extras > $OUT/$c/bench.json
+    python3 bench.py --full $ARGS --steps 100 --warmup 20 --no-cpu-baseline --no-extras > $OUT/$c/bench.json
   timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/$c/fetch -o run -- \
-    python3 bench.py $ARGS --steps 30 --warmup 5 --no-cpu-baseline --no-extras > /dev/null
+    python3 bench.py --full $ARGS --steps 30 --warmup 5 --no-cpu-baseline --no-extras > /dev/null
   timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/$c/write -o run -- \
-    python3 bench.py $ARGS --steps 30 --warmup 5 --no-cpu-baseline --no-extras > /dev/null
+    python3 bench.py --full $ARGS --steps 30 --warmup 5 --no-cpu-baseline --no-extras > /dev/null
   python3 tools/pmc_summary.py $OUT/$c > $OUT/$c/pmc.json
   echo "profiled $c"
 done

@@ -48,3 +48,36 @@ def test_cpu_info_counts_usable_cores():
     info = bench.cpu_info()
     assert 1 <= info["usable"] <= info["affinity"]
     assert info["usable"] == len(os.sched_getaffinity(0)) or info["cgroup_quota_cpus"]
+
+
+def test_plain_run_is_the_default_and_full_is_an_option():
+    sys.path.insert(0, ROOT)
+    import bench
+
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d"
+
+
+def test_output_sample_is_fixed_and_within_its_budget():
+    """--dump-outputs' obs sample: the same rows on every call (a seeded draw over the stacked row
+    index, ascending), every row when they fit, float32."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+
+    import bench
+
+    a = torch.arange(40 * 6, dtype=torch.float32).view(40, 6)
+    b = torch.arange(40 * 6, 70 * 6, dtype=torch.float32).view(30, 6)
+    whole = bench._sample_rows([a, b])
+    assert whole.dtype == np.float32 and np.array_equal(whole, torch.cat([a, b]).numpy())
+    s1 = bench._sample_rows([a, b], budget=10 * 6 * 4)
+    s2 = bench._sample_rows([a, b], budget=10 * 6 * 4)
+    assert s1.shape == (10, 6) and np.array_equal(s1, s2)
+    rows = (s1[:, 0] / 6).astype(int)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(s1, torch.cat([a, b]).numpy()[rows])
+    assert rows.min() < 40 <= rows.max()  # rows of both blocks (this seed's draw)
+    u8 = torch.arange(200, dtype=torch.uint8).view(-1, 1)
+    assert np.array_equal(bench._sample_rows([u8])[:, 0], np.arange(200, dtype=np.float32))

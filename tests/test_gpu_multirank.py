@@ -43,7 +43,7 @@ def test_two_ranks_c4():
 
 
 def test_two_ranks_c5_is_the_default_multi_gpu_line():
-    d = _run("--envs", "8")  # no --config: N > 1 measures C5
+    d = _run("--envs", "8", "--full")  # no --config: N > 1 measures C5; --full: the stored / decoded passes too
     assert d["n_gpus"] == 2 and d["config"]["workload"].startswith("C5")
     assert d["value_kind"] == "delivered" and d["decoded"]["value"] > 0 and d["stored"]["value"] > 0
     # the root stored every row in the realm of both ranks: the rows/s equal the alive agent-steps/s

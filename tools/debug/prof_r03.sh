@@ -1,8 +1,8 @@
 # one-scan cull: parity / wrapper / full-size tests and C2 / C4 stamps; then the round-3
 # rocprofv3 summaries
-cd $GRAFT_REPO_ROOT && export TMPDIR=/tmp && mkdir -p gpurun_out/r3 && set -o pipefail
+cd "$(dirname "$0")/../.." && export TMPDIR=/tmp && mkdir -p bench_out/r3 && set -o pipefail
 timeout -k 10 600 python -u -m pytest -x -q --timeout 150 --timeout-method thread tests/test_gpu_parity.py \
-  tests/test_gpu_wrapper.py tests/test_gpu_fullsize.py tests/test_gpu_observe.py > gpurun_out/r3/tests.log 2>&1 || exit 1
-STAMPS_STAGGER=64 timeout -k 10 200 python tools/stamps.py C2 256 40 > gpurun_out/r3/stamps_C2.txt 2>&1 || exit 1
-STAMPS_STAGGER=64 timeout -k 10 200 python tools/stamps.py C4 512 40 > gpurun_out/r3/stamps_C4.txt 2>&1 || exit 1
+  tests/test_gpu_wrapper.py tests/test_gpu_fullsize.py tests/test_gpu_observe.py > bench_out/r3/tests.log 2>&1 || exit 1
+STAMPS_STAGGER=64 timeout -k 10 200 python tools/stamps.py C2 256 40 > bench_out/r3/stamps_C2.txt 2>&1 || exit 1
+STAMPS_STAGGER=64 timeout -k 10 200 python tools/stamps.py C4 512 40 > bench_out/r3/stamps_C4.txt 2>&1 || exit 1
 bash profiles/run_rocprof.sh r03 C4 C4-native C5 C2 C3

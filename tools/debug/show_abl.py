@@ -1,6 +1,6 @@
-"""Summarise gpurun_out/abl/*.json (abl_run.sh): value and kernel_ms per library and repetition."""
+"""Summarise bench_out/abl/*.json (abl_run.sh): value and kernel_ms per library and repetition."""
 import glob, json, os, sys
-d = sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/abl"
+d = sys.argv[1] if len(sys.argv) > 1 else "bench_out/abl"
 for f in sorted(glob.glob(os.path.join(d, "*.json"))):
     try:
         j = json.loads(open(f).read().strip().splitlines()[-1])

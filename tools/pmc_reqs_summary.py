@@ -2,7 +2,7 @@
 """Summarise tools/debug/pmc_tick_reqs.sh output: tick-kernel HBM read/write requests by size
 class (TCC_EA0_RDREQ_32B/_64B/_128B, TCC_EA0_WRREQ/_64B) per dispatch, and the bytes they carry.
 
-  python tools/pmc_reqs_summary.py gpurun_out/pmc_reqs > profiles/r02/tick_reqs.json
+  python tools/pmc_reqs_summary.py bench_out/pmc_reqs > profiles/r02/tick_reqs.json
 """
 
 import csv
