@@ -1,0 +1,70 @@
+/*
+ * nmmo_heads.h — C-ABI of the fused masked action heads (libnmmo_heads.so).
+ *
+ * Every policy of the reference ends in the same step (baseline_policy.py:245-262): per action
+ * head, masked_fill(mask == 0, -1e9) on the head's logits, a Categorical, then sample / log_prob
+ * / entropy. nmh_forward does that for all heads of a row in one gfx950 kernel, reading the mask
+ * in place from the obs row; nmh_backward is its gradient with respect to the logits. The
+ * semantics are frozen in SPEC.md §15.
+ *
+ * Conventions (those of nmmo_hip.h): every call returns 0 or a negative NMH_E_* code and never
+ * aborts; nmh_last_error() returns a thread-local message. Argument errors are reported without
+ * touching a GPU. Every buffer is a caller-owned DEVICE pointer; work is enqueued on `stream`
+ * (a hipStream_t, NULL = default stream) with no synchronisation and no allocation inside.
+ */
+#ifndef NMMO_HEADS_H
+#define NMMO_HEADS_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define NMH_API __attribute__((visibility("default")))
+
+#define NMH_OK 0
+#define NMH_E_INVALID (-1) /* bad argument */
+#define NMH_E_HIP (-2)     /* HIP runtime error */
+
+#define NMH_MAX_HEADS 16
+#define NMH_MAX_DIM 2048
+
+/* The heads of one row, concatenated: head k is dims[k] consecutive entries of a logits row and
+ * of a mask row. 1 <= n_heads <= NMH_MAX_HEADS, 1 <= dims[k] <= NMH_MAX_DIM. */
+typedef struct NmhHeads {
+  int32_t n_heads;
+  int32_t dims[NMH_MAX_HEADS];
+} NmhHeads;
+
+#define NMH_MASK_F32 0 /* float32 mask, legal iff value > 0 (the flat obs row's prefix) */
+#define NMH_MASK_U8 1  /* byte mask, legal iff byte != 0 (native obs row, bool tensors) */
+
+/* Strides are in elements of the row's type and must be >= sum(dims). Rows need no alignment.
+ *
+ * actions_in NULL: sample (seed, offset, row_base select the draws: row r, head k uses the
+ * philox counter (row_base + r, k, offset)); else evaluate the given [n_rows, n_heads] actions.
+ * actions_out [n_rows, n_heads] gets the sampled actions, or a copy of actions_in.
+ * logprob / entropy [n_rows]: sums over heads. lse / head_entropy [n_rows, n_heads]: per head,
+ * what nmh_backward needs. n_rows == 0 is a no-op. */
+NMH_API int nmh_forward(const NmhHeads* hd, int32_t n_rows, const float* logits, int64_t logits_stride,
+                        const void* mask, int64_t mask_stride, int32_t mask_kind, const int32_t* actions_in,
+                        uint64_t seed, uint64_t offset, uint32_t row_base, int32_t* actions_out,
+                        float* logprob, float* entropy, float* lse, float* head_entropy, void* stream);
+
+/* d(sum_r g_logprob[r] logprob[r] + g_entropy[r] entropy[r]) / d logits into g_logits (row stride
+ * g_stride >= sum(dims)); every entry of the sum(dims) prefix of every row is written, zeros
+ * included. g_logprob / g_entropy [n_rows]; either may be NULL (= zeros). */
+NMH_API int nmh_backward(const NmhHeads* hd, int32_t n_rows, const float* logits, int64_t logits_stride,
+                         const void* mask, int64_t mask_stride, int32_t mask_kind, const int32_t* actions,
+                         const float* lse, const float* head_entropy, const float* g_logprob,
+                         const float* g_entropy, float* g_logits, int64_t g_stride, void* stream);
+
+NMH_API const char* nmh_last_error(void);
+/* "src=<hash of the sources the library was compiled from> arch=gfx950 fp_contract=off" */
+NMH_API const char* nmh_build_info(void);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

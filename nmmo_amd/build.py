@@ -1,5 +1,5 @@
-"""Build libnmmo_hip.so in-tree with hipcc for gfx950 (no JIT cache: the .so ships with the repo
-snapshot to the GPU box)."""
+"""Build libnmmo_hip.so and libnmmo_heads.so in-tree with hipcc for gfx950 (no JIT cache: the
+libraries ship with the repo snapshot to the GPU box)."""
 
 from __future__ import annotations
 
@@ -17,6 +17,11 @@ SOURCES = ["mapgen.hip", "tick.hip", "obs.hip", "wrap.hip", "storage.hip", "wire
            "flat_obs.hip", "p2p.hip", "capi.hip"]
 HEADERS = ["agent_obs.h", "common.h", "kernels.h", "wire.h"]
 ARCH = os.environ.get("NMMO_OFFLOAD_ARCH", "gfx950")
+# the fused action heads (include/nmmo_heads.h): a library of their own, so libnmmo_hip.so's
+# exports, SOURCES / HEADERS and source_hash() stay what the C-ABI tests and bench.py pin
+HEADS_LIB_PATH = os.path.join(LIB_DIR, "libnmmo_heads.so")
+HEADS_SOURCES = ["heads.hip"]
+HEADS_HEADERS = ["common.h"]
 
 
 def _hipcc() -> str:
@@ -36,6 +41,24 @@ def source_hash() -> str:
         with open(f, "rb") as fh:
             h.update(os.path.basename(f).encode() + b"\0" + fh.read())
     return h.hexdigest()[:16]
+
+
+def heads_source_hash() -> str:
+    """source_hash() of libnmmo_heads.so: heads.hip, the headers it includes, its C interface."""
+    h = hashlib.sha256()
+    for f in [os.path.join(CSRC, f) for f in HEADS_SOURCES + HEADS_HEADERS] + [
+            os.path.join(HERE, "..", "include", f) for f in ("nmmo_hip.h", "nmmo_heads.h")]:
+        with open(f, "rb") as fh:
+            h.update(os.path.basename(f).encode() + b"\0" + fh.read())
+    return h.hexdigest()[:16]
+
+
+def heads_stale() -> bool:
+    """True unless libnmmo_heads.so exists and embeds the current heads source hash."""
+    if not os.path.exists(HEADS_LIB_PATH):
+        return True
+    with open(HEADS_LIB_PATH, "rb") as fh:
+        return ("src=" + heads_source_hash()).encode() not in fh.read()
 
 
 def stale() -> bool:
@@ -79,5 +102,22 @@ def build(force: bool = False, verbose: bool = False, stamps: bool = False) -> s
     return out
 
 
+def build_heads(force: bool = False, verbose: bool = False) -> str:
+    """libnmmo_heads.so (nmmo_amd/heads.py), with the product library's flags."""
+    if not force and not heads_stale():
+        return HEADS_LIB_PATH
+    os.makedirs(LIB_DIR, exist_ok=True)
+    tmp = HEADS_LIB_PATH + ".tmp"
+    cmd = [_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Werror",
+           "-ffp-contract=off", f'-DNMH_SRC_HASH="{heads_source_hash()}"', "-shared",
+           *[os.path.join(CSRC, f) for f in HEADS_SOURCES], "-o", tmp]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+    os.replace(tmp, HEADS_LIB_PATH)
+    return HEADS_LIB_PATH
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
+    print(build_heads(force="--force" in sys.argv, verbose=True))

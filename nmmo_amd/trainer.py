@@ -61,10 +61,18 @@ class TrainConfig:
 class MaskedLinearAgent(nn.Module):
     """A small stand-in policy: the 15x15 Tile materials and the agent's own tick through one
     hidden layer, a linear head per action with illegal entries masked out by the obs's
-    ActionTargets, and a value head."""
+    ActionTargets, and a value head.
 
-    def __init__(self, task_dim: int = 2048, hidden: int = 64):
+    `fused_heads=True` runs the heads as one `heads.masked_heads` call (the HIP kernels of
+    SPEC.md §15) instead of the loop of Categoricals; sampling then draws from philox under
+    `seed` with a counter that advances on every sampling call, not from torch's generator, and
+    sampled actions are int32."""
+
+    def __init__(self, task_dim: int = 2048, hidden: int = 64, fused_heads: bool = False, seed: int = 0):
         super().__init__()
+        self.fused_heads = bool(fused_heads)
+        self.seed = int(seed)
+        self.draws = 0  # sampling calls so far: the `offset` of the next one
         lay = layout.flat_layout(task_dim)
         self.o_tile = lay["Tile"].offset
         self.o_tick = lay["CurrentTick"].offset
@@ -79,6 +87,13 @@ class MaskedLinearAgent(nn.Module):
         tick = obs[:, self.o_tick:self.o_tick + 1] / 1024.0
         h = self.encoder(torch.cat([mat, tick], 1))
         logits = self.actor(h)
+        if self.fused_heads:
+            from .heads import masked_heads
+
+            acts, logp, ent = masked_heads(logits, obs, self.dims, action, seed=self.seed, offset=self.draws)
+            if action is None:
+                self.draws += 1
+            return acts, logp, ent, self.value(h)
         masks = obs[:, :self.mask_off[-1]] > 0
         acts, logp, ent = [], 0.0, 0.0
         for k, n in enumerate(self.dims):

@@ -2,7 +2,8 @@
 reference trainer's agent_SPS (clean_pufferl.py:364-376) with the HIP stepper, HBM storage and the
 small stand-in policy, plus the train side (sort, GAE, PPO epochs) per update.
 
-Usage (GPU box): python tools/bench_trainer.py [envs] [batch_size] [updates]
+Usage (GPU box): python tools/bench_trainer.py [envs] [batch_size] [updates] [--fused-heads]
+(--fused-heads: the agent's action heads run as the fused HIP kernels, nmmo_amd/heads.py)
 """
 
 import json
@@ -20,14 +21,16 @@ from nmmo_amd.trainer import DeviceTrainer, MaskedLinearAgent, TrainConfig  # no
 
 
 def main():
-    envs = int(sys.argv[1]) if len(sys.argv) > 1 else 64
-    batch = int(sys.argv[2]) if len(sys.argv) > 2 else 32768
-    updates = int(sys.argv[3]) if len(sys.argv) > 3 else 3
+    fused = "--fused-heads" in sys.argv
+    argv = [a for a in sys.argv if a != "--fused-heads"]
+    envs = int(argv[1]) if len(argv) > 1 else 64
+    batch = int(argv[2]) if len(argv) > 2 else 32768
+    updates = int(argv[3]) if len(argv) > 3 else 3
     torch.manual_seed(1)
     cfg = Config.preset("C4", early_stop_agent_num=8)
     eng = NmmoEngine(cfg, envs, seed=1)
     eng.reset()
-    agent = MaskedLinearAgent(cfg.TASK_EMBED_DIM).cuda()
+    agent = MaskedLinearAgent(cfg.TASK_EMBED_DIM, fused_heads=fused, seed=1).cuda()
     tc = TrainConfig(batch_size=batch, total_timesteps=batch * (updates + 1))
     tr = DeviceTrainer(eng, agent, tc)
     tr.evaluate()  # warm-up (allocator, kernels)
@@ -37,7 +40,9 @@ def main():
         ev.append(tr.evaluate())
         trn.append(tr.train())
     out = {
-        "workload": f"C4 {envs} envs x 128 agents, flat obs, batch_size {batch}, MaskedLinearAgent",
+        "workload": f"C4 {envs} envs x 128 agents, flat obs, batch_size {batch}, MaskedLinearAgent"
+                    + (", fused heads" if fused else ""),
+        "fused_heads": fused,
         "agent_SPS": round(sum(e["agent_SPS"] for e in ev) / len(ev)),
         "SPS": round(sum(e["SPS"] for e in ev) / len(ev)),
         "eval_time_s": round(sum(e["eval_time"] for e in ev) / len(ev), 4),
