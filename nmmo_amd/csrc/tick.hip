@@ -85,6 +85,7 @@ struct Ctx {
   bool tmap;         // DevState::tmap: a task reads the material map at the rewards
   bool tsee;         // DevState::tsee: a task counts window entities (the rewards' slot words in ft)
   int evcap, tick1;  // ring rows (0 = no event log); tick + 1 (the events' tick column)
+  int ev_end;        // events logged once the current scan's are in (ev_put: rows a later event of the scan takes)
   int S, P, N, IC;
   bool items, exch, prof, equip;
   bool foreign;      // !prof and DevState::foreign is set: respawn reads the map bank
@@ -301,6 +302,7 @@ __device__ __forceinline__ Ctx make_ctx(unsigned char* smem, const DevState& st,
   c.evcap = st.cfg.event_cap > 0 ? st.cfg.event_cap : 0;
   c.evg = c.evcap ? st.events + (size_t)e * c.evcap * NMMO_EVENT_COLS : nullptr;
   c.tick1 = 0;
+  c.ev_end = 0;
   c.S = S;
   c.P = P;
   c.N = st.N;
@@ -677,6 +679,14 @@ __device__ __forceinline__ void ev_put(const Ctx& c, int idx, int p, int code, i
                                        int number, int gold, int target) {
   if (c.tev) task_accumulate(c, p, code, type, level, number, gold, target);
   if (!c.evcap) return;
+  // A scan that logs more events than the ring has rows puts two of them on one row from two
+  // threads: only the later event (SPEC §11: row k lives at (k - 1) mod event_cap) is written.
+  // Scans follow each other across barriers, so a later scan's row lands after this one's.
+  // Every parallel emitter therefore sets c.ev_end (block-uniform: evn + the scan's event total)
+  // before its first ev_put: ev_append and ring_ev_append do, and so do the hand-rolled scans of
+  // Buy, Give, Move / Sell and the cull; a new scan that emits from several threads must too.
+  // Thread 0's serial loot walk leaves it stale-low, which only keeps every row.
+  if (idx + c.evcap < c.ev_end) return;
   // ring row: a mask for power-of-two rings (the default 4,096; a uniform branch), else a
   // division, ~20 dependent instructions per event on this latency-bound path
   const int row = (c.evcap & (c.evcap - 1)) == 0 ? (idx & (c.evcap - 1)) : idx % c.evcap;
@@ -697,6 +707,7 @@ template <typename F>
 __device__ __forceinline__ void ev_append(Ctx& c, int& evn, int n, F&& emit) {
   int tot;
   const int pre = block_prefix_sum(n, wtot_next(c), &tot);
+  c.ev_end = evn + tot;
   if (n) emit(evn + pre);
   evn += tot;
 }
@@ -709,6 +720,7 @@ __device__ __forceinline__ void ring_ev_append(Ctx& c, int row, int& evn, int ne
   int tot;
   const int pre = block_prefix_sum((row >= 0 ? 1 : 0) | nev << 16, wtot_next(c), &tot);
   if (row >= 0) c.iring[(fb + (pre & 0xFFFF)) % c.IC] = (int16_t)row;
+  c.ev_end = evn + (tot >> 16);
   if (nev) emit(evn + (pre >> 16));
   evn += tot >> 16;
   if (threadIdx.x == 0) c.E[E_ITEM_FREE_COUNT] += tot & 0xFFFF;
@@ -1929,6 +1941,7 @@ __device__ __forceinline__ void tick_env(Ctx& c, Heads hd, bool defer, DepQ dq, 
         };
         const int nok = __popc(okm[0]) + __popc(okm[1]) + __popc(okm[2]) + __popc(okm[3]);
         const int nfr = __popc(frm[0]) + __popc(frm[1]) + __popc(frm[2]) + __popc(frm[3]);
+        c.ev_end = evn + 2 * nok;
         if (ok) {
           const int i = evn + 2 * below(okm);
           if (evon) {
@@ -2011,6 +2024,7 @@ __device__ __forceinline__ void tick_env(Ctx& c, Heads hd, bool defer, DepQ dq, 
         int tot;
         const int pre = block_prefix_sum((freed >= 0 ? 1 : 0) | nev << 16, wtot_next(c), &tot);
         if (freed >= 0) c.iring[(fb + (pre & 0xFFFF)) % c.IC] = (int16_t)freed;
+        c.ev_end = evn + (tot >> 16);
         if (nev) {
           int i = evn + (pre >> 16);
           if (did_item) ev_put(c, i++, s, EV_GIVE_ITEM, it_type(gw), it_level(gw), it_qty(gw), 0, TF(F_ID, tg));
@@ -2181,6 +2195,7 @@ __device__ __forceinline__ void tick_env(Ctx& c, Heads hd, bool defer, DepQ dq, 
     const int nl = it_type(sw) ? 1 : 0;
     int tot;
     const int pre = block_prefix_sum((gf > 0 ? 1 : 0) | (nl << 16), wtot_next(c), &tot);
+    c.ev_end = evn + (tot & 0xFFFF) + (tot >> 16);
     if (gf > 0) ev_put(c, evn + (pre & 0xFFFF), s, EV_GO_FARTHEST, 0, 0, gf, 0, 0);
     if (nl)
       ev_put(c, evn + (tot & 0xFFFF) + (pre >> 16), s, EV_LIST_ITEM, it_type(sw), it_level(sw), it_qty(sw),
@@ -2207,6 +2222,7 @@ __device__ __forceinline__ void tick_env(Ctx& c, Heads hd, bool defer, DepQ dq, 
   const int ndead = ctot & 1023, npdead = (ctot >> 10) & 255;
   if (s < P) c.died[s] = dead ? 1 : 0;
   if (evon) {  // AGENT_CULLED in slot order (players are slots 0..P-1: the same prefix)
+    c.ev_end = evn + npdead;
     if (dead && s < P) ev_put(c, evn + ppos, s, EV_AGENT_CULLED, 0, 0, 0, 0, 0);
     evn += npdead;
   }
