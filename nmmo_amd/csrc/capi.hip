@@ -959,7 +959,7 @@ int nmmo_exp_store(NmmoHandle* h, const NmmoExperience* x, const NmmoStoreInput*
 }
 
 int nmmo_exp_sort(const NmmoExperience* x, int32_t* idxs, int32_t* scratch, void* stream) {
-  if (int rc = check_exp(x)) return rc;
+  if (int rc = check_exp(x, false)) return rc;  // reads no obs: compact storage sorts too
   if (!idxs || !scratch) return fail(NMMO_E_INVALID, "null idxs/scratch");
   HIP_TRY(launch_sort(*x, idxs, scratch, (hipStream_t)stream));
   return NMMO_OK;
@@ -967,7 +967,7 @@ int nmmo_exp_sort(const NmmoExperience* x, int32_t* idxs, int32_t* scratch, void
 
 int nmmo_exp_gae(const NmmoExperience* x, const int32_t* idxs, int32_t batch_size, double gamma, double gae_lambda,
                  float* advantages, void* stream) {
-  if (int rc = check_exp(x)) return rc;
+  if (int rc = check_exp(x, false)) return rc;
   if (!idxs || !advantages) return fail(NMMO_E_INVALID, "null idxs/advantages");
   if (batch_size <= 0 || batch_size >= x->capacity)
     return fail(NMMO_E_SIZE, "batch_size must be in [1, capacity - 1]");
