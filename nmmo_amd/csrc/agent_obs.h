@@ -31,10 +31,12 @@ constexpr int kAoAgents = NMMO_AO_AGENTS;  // agents per workgroup
 constexpr int kAoRows = kMaxSlots / 64;   // packed datastore-row words per lane
 constexpr uint32_t kAoEmpty = 0xFFFFFFFFu;
 static_assert(kSize <= 256 && kMaxSlots <= 2 * 256 && kMaxSlots % 64 == 0, "packed entity word; two slots per thread (>= 256 threads)");
-__host__ __device__ inline int ao_stride(int S) { return ((S + 1) >> 1 | 1) << 1; }  // int16, odd dword count
-__host__ __device__ inline size_t ao_entity_lds(int S) {  // T | pk
-  return (((size_t)NMMO_N_ENTITY_COLS * ao_stride(S) * 2 + 15) & ~(size_t)15) + (size_t)(kMaxSlots + 64) * 4;
+__host__ __device__ constexpr int ao_stride(int S) { return ((S + 1) >> 1 | 1) << 1; }  // int16, odd dword count
+__host__ __device__ constexpr size_t ao_columns_lds(int S) {  // T
+  return ((size_t)NMMO_N_ENTITY_COLS * ao_stride(S) * 2 + 15) & ~(size_t)15;
 }
+constexpr size_t kAoPkBytes = (size_t)(kMaxSlots + 64) * 4;
+__host__ __device__ constexpr size_t ao_entity_lds(int S) { return ao_columns_lds(S) + kAoPkBytes; }  // T | pk
 __host__ __device__ inline uint32_t ao_pack(int slot, int row, int col, bool immune, bool danger, bool player) {
   return (uint32_t)(row & 255) | (uint32_t)(slot & 255) << 8 | (uint32_t)(col & 255) << 16 | (uint32_t)(slot >> 8) << 24 |
          (immune ? 1u << 25 : 0u) | (danger ? 1u << 26 : 0u) | (player ? 1u << 27 : 0u);
@@ -229,6 +231,10 @@ __device__ __forceinline__ void ao_env_group(int n_envs, int G, int& e, int& g) 
 // LDS once per workgroup (every thread; one barrier inside): ws[(la * 15 + row) * 5 + k] = the 5
 // aligned dwords holding window row `row` of agent la (its 15 materials start at byte
 // (col - kVision) & 3 of them: 160 is a multiple of 4), is[la * kInv + k] = its item word k.
+// With kRowDw = 4 the row is realigned while staging (v_alignbyte on the 5 loaded dwords): its 15
+// materials start at byte 0 of 4 dwords, and the agent loop needs no column term.
+// `before_writes` runs after the loads are issued and ahead of the first LDS write (every thread):
+// a kernel that aliases `ws` / `is` onto LDS it has read until here puts its barrier there.
 // The agent loops then issue no global load. On gfx9 vmcnt counts stores as well as loads and
 // retires them in issue order, so a load prefetched inside the loop is waited on at the loop's
 // back edge together with the stores issued after it -- as many of them as the compiler cannot
@@ -236,7 +242,7 @@ __device__ __forceinline__ void ao_env_group(int n_envs, int G, int& e, int& g) 
 // the next agent started.
 constexpr int kAoWinRowBytes = 20;
 constexpr int kAoWinAgentBytes = 15 * kAoWinRowBytes;  // 300
-__host__ __device__ inline size_t ao_win_lds(int agents = kAoAgents) {
+__host__ __device__ constexpr size_t ao_win_lds(int agents = kAoAgents) {
   return (size_t)agents * kAoWinAgentBytes + (size_t)agents * kInv * 8;
 }
 // positions of agents not in the realm are clamped so their (unused) window reads stay in the map
@@ -245,9 +251,10 @@ __device__ __forceinline__ int ao_clamp_pos(int x) { return min(max(x, kVision),
 struct AoNoop {
   __device__ void operator()() const {}
 };
-template <int kAgents = kAoAgents, typename F = AoNoop>
+template <int kAgents = kAoAgents, int kRowDw = kAoWinRowBytes / 4, typename F = AoNoop, typename B = AoNoop>
 __device__ inline void ao_stage_windows(const ObsParams& p, int e, int g, const int16_t* T, int Sp, uint32_t* ws, uint2* is,
-                                        F before_barrier = F()) {
+                                        F before_barrier = F(), B before_writes = B()) {
+  static_assert(kRowDw == 4 || kRowDw == 5, "window row: 5 aligned dwords, or 4 realigned");
   const int tid = threadIdx.x, P = p.P;
   const int la = tid / 15, row = tid - 15 * la, a = g * kAgents + la;
   const bool win = tid < kAgents * 15 && a < P;
@@ -258,26 +265,32 @@ __device__ inline void ao_stage_windows(const ObsParams& p, int e, int g, const 
     const uint32_t* src = reinterpret_cast<const uint32_t*>(p.mat + (size_t)e * kTiles) + (base >> 2);
 #pragma unroll
     for (int k = 0; k < 5; k++) d[k] = src[k];
+    if constexpr (kRowDw == 4) {
+#pragma unroll
+      for (int k = 0; k < 4; k++) d[k] = __builtin_amdgcn_alignbyte(d[k + 1], d[k], (uint32_t)(c - kVision) & 3u);
+    }
   }
   uint2 iw = make_uint2(0u, 0u);
   const bool itm = tid < kAgents * kInv && g * kAgents + tid / kInv < P;
   if (itm) iw = p.items[((size_t)e * P + g * kAgents) * kInv + tid];
+  before_writes();
   if (win) {
 #pragma unroll
-    for (int k = 0; k < 5; k++) ws[tid * 5 + k] = d[k];  // tid = la * 15 + row
+    for (int k = 0; k < kRowDw; k++) ws[tid * kRowDw + k] = d[k];  // tid = la * 15 + row
   }
   if (tid < kAgents * kInv) is[tid] = iw;
   before_barrier();
   __syncthreads();
 }
 // Per-lane byte offsets of window tiles t = lane + 64 i (i < 4) in an agent's staged rows
-// (row(t) * 20 + col(t)), two 16-bit values per register
+// (row(t) * kRowBytes + col(t)), two 16-bit values per register
+template <int kRowBytes = kAoWinRowBytes>
 __device__ __forceinline__ void ao_win_offsets(int (&wo)[2]) {
   wo[0] = wo[1] = 0;
 #pragma unroll
   for (int i = 0; i < 4; i++) {
     const int t = lane_id() + 64 * i;
-    const int o = t < 225 ? (t / 15) * kAoWinRowBytes + t % 15 : 0;
+    const int o = t < 225 ? (t / 15) * kRowBytes + t % 15 : 0;
     wo[i >> 1] |= o << (16 * (i & 1));
   }
 }

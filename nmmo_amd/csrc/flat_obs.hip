@@ -18,7 +18,8 @@
 //  - the env's Entity columns staged with an odd dword stride (conflict-free lane-per-field reads),
 //    the window compaction from packed datastore-row words held in registers, and the workgroup's
 //    window rows and item words staged in LDS up front, so the agent loop issues no global load
-//    (except a Task section to rewrite, once per task change, and listings past the staged 256);
+//    (except a Task section to rewrite, once per task change, and the listings whose item words
+//    did not fit LDS: none up to 256 listings);
 //  - every store goes to the row's wave-uniform base (SGPRs) plus a per-lane constant offset.
 #include "agent_obs.h"
 
@@ -50,7 +51,7 @@ __device__ uint64_t fo_wave_buf[1 << 15][6];  // per wave: entry, staged, window
 #define NMMO_FO_TASK_BATCH 8
 #endif
 constexpr int kFoTaskBatch = NMMO_FO_TASK_BATCH;  // Task floats per lane loaded before their stores
-constexpr int kFoStagedListings = 256;  // listings whose item words are staged (Market rows)
+constexpr int kFoStagedListings = 64;   // listings whose item words are staged at the least (fo_staged)
 constexpr int kFoChunks = 25;           // 64-entry chunks over the 1,586 mask entries (+ id, tick)
 static_assert(kFoChunks * 64 >= kMaskN + 2 && (kFoChunks - 1) * 64 < kMaskN, "mask chunks");
 static_assert(sec_flat(2) == 104 && sec_flat(3) == 104 + NMMO_MARKET_ROWS + 1, "Buy.MarketItem bits");
@@ -60,13 +61,44 @@ constexpr int kFoBuyLo = sec_flat(2);
 constexpr int kFoId = kMaskN, kFoEntity = kFoId + 2, kFoInv = kFoEntity + kNObs * NMMO_N_ENTITY_COLS,
               kFoMarket = kFoInv + kInv * 16, kFoTask = kFoMarket + NMMO_MARKET_ROWS * 16;
 
-// LDS: agent_obs.h's entity staging | listings (price | owner << 8, u16) | the first 256 listings'
-// item words | per-wave visible rows | the workgroup's staged window rows and item words.
-// 38.7 KB at S = 384: 4 workgroups per CU.
-__host__ __device__ inline size_t fo_lds_bytes(int S) {
-  return ao_entity_lds(S) + (size_t)NMMO_MARKET_ROWS * 2 + (size_t)kFoStagedListings * 8 +
-         (size_t)kAoWaves * 128 * 4 + ao_win_lds();
+// LDS: agent_obs.h's Entity columns T | the listings' pool | per-wave visible rows | the workgroup's
+// staged window rows (16 B each, realigned) | its item words. 31,936 B at S = 384: 5 workgroups per
+// CU (LDS is allocated in 1,280-B granules, so 5 fit up to 32,000 B, not 32,768).
+// The listings' pool (2,560 B) is filled from both ends: price | owner << 8 (u16) of all nm listings
+// upwards from its start, the item words of the first fo_staged(nm) listings downwards from its
+// end -- every listing's up to nm = 256, 64 at nm = 1,024 (the pool's size: kFoStagedListings).
+// Two more regions are shared by data that is never live together:
+//  - the packed datastore-row words (pk, agent_obs.h) lie in the window rows' region: they are dead
+//    once every lane holds its pr[] words, and the window rows are written after a barrier that
+//    follows those loads (ao_stage_windows' before_writes);
+//  - at S = 384 the item words lie in T's F_ROW and F_COL columns (adjacent, 1,544 B): after that
+//    barrier nothing reads them -- an agent's own position is kept in a register (my_rc) and a
+//    visible entity's comes from its packed word (ao_row / ao_col: the values the window test used).
+//    A smaller S has smaller columns and LDS to spare: the item words follow the window rows.
+constexpr int kFoVisw = (kNObs + 3) & ~3;            // visible-row words per wave (the compaction writes pos < kNObs)
+constexpr int kFoWinRowBytes = 16, kFoWinAgentBytes = 15 * kFoWinRowBytes;
+constexpr size_t kFoWinBytes = (size_t)kAoAgents * kFoWinAgentBytes, kFoItemBytes = (size_t)kAoAgents * kInv * 8;
+static_assert(F_COL == F_ROW + 1 && kAoPkBytes <= kFoWinBytes, "shared LDS regions");
+__host__ __device__ constexpr bool fo_items_in_T(int S) {
+  return (size_t)2 * ao_stride(S) * 2 >= kFoItemBytes && (F_ROW * ao_stride(S) * 2) % 8 == 0;
 }
+constexpr int kFoListPool = NMMO_MARKET_ROWS * 2 + kFoStagedListings * 8;
+// listings whose item words fit the pool beside nm price | owner entries (8-B aligned)
+__host__ __device__ constexpr int fo_staged(int nm) {
+  return nm < ((kFoListPool - ((2 * nm + 7) & ~7)) >> 3) ? nm : (kFoListPool - ((2 * nm + 7) & ~7)) >> 3;
+}
+static_assert(fo_staged(NMMO_MARKET_ROWS) == kFoStagedListings && fo_staged(256) == 256 && fo_staged(257) == 255 &&
+                  fo_staged(0) == 0 && kFoListPool % 16 == 0, "listings' pool");
+__host__ __device__ constexpr size_t fo_lds_bytes(int S) {
+  return ao_columns_lds(S) + (size_t)kFoListPool +
+         (size_t)kAoWaves * kFoVisw * 4 + kFoWinBytes + (fo_items_in_T(S) ? 0 : kFoItemBytes);
+}
+constexpr size_t kFoLdsGranule = 1280;  // gfx950's LDS allocation unit (tools/occupancy_probe.hip)
+// (the product shape; an A/B build with another NMMO_AO_AGENTS keeps its item words after the window rows)
+static_assert(kAoAgents != 16 ||
+                  (5 * fo_lds_bytes(kMaxSlots) <= 160 * 1024 && fo_items_in_T(kMaxSlots) &&
+                   5 * ((fo_lds_bytes(kMaxSlots) + kFoLdsGranule - 1) / kFoLdsGranule * kFoLdsGranule) <= 160 * 1024),
+              "5 workgroups per CU");
 
 // Low 64 bits of the 128-bit field (hi:lo) shifted left by kSh (right when negative): the part of a
 // section whose bit 0 sits at chunk bit kSh.
@@ -225,17 +257,19 @@ typedef const __attribute__((address_space(4))) ObsParams* FoArgs;  // the kerne
 
 // kS: the slot count when known at compile time (C3 / C4: 128 players + 256 NPCs), 0 = p.S. With
 // it the staged-column offsets are immediates instead of uniform values the agent loop keeps live.
+// 5 waves per SIMD (5 workgroups of 4 waves per CU): 96 VGPRs, which the kernel fits without scratch.
 template <bool kWrap, int kS>
-__global__ void __launch_bounds__(64 * kAoWaves) flat_obs_kernel(ObsParams p) {
+__global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per_eu(5, 5))) flat_obs_kernel(ObsParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int S = kS ? kS : p.S, P = p.P, Sp = ao_stride(S), tdim = p.task_dim, elems = kFoTask + tdim + 225 * 3;
   int16_t* T = reinterpret_cast<int16_t*>(smem);
-  uint32_t* pk = reinterpret_cast<uint32_t*>(smem + ao_entity_lds(S) - (size_t)(kMaxSlots + 64) * 4);
-  uint16_t* mpo = reinterpret_cast<uint16_t*>(pk + kMaxSlots + 64);            // [1024] price | owner << 8
-  uint2* mitem = reinterpret_cast<uint2*>(mpo + NMMO_MARKET_ROWS);            // [256] listed item words
-  uint32_t* visw_all = reinterpret_cast<uint32_t*>(mitem + kFoStagedListings);  // [4][128]
-  uint32_t* wst = visw_all + kAoWaves * 128;                                   // [16][15][5] window rows
-  uint2* ist = reinterpret_cast<uint2*>(wst + kAoAgents * kAoWinAgentBytes / 4);  // [16][12] item words
+  uint16_t* mpo = reinterpret_cast<uint16_t*>(smem + ao_columns_lds(S));       // [1024] price | owner << 8
+  uint32_t* visw_all = reinterpret_cast<uint32_t*>(mpo) + kFoListPool / 4;       // [4][100]
+  uint2* mtop = reinterpret_cast<uint2*>(visw_all) - 1;  // mtop[-k]: listing k's item word (k < fo_staged(nm))
+  uint32_t* wst = visw_all + kAoWaves * kFoVisw;                               // [16][15][4] window rows
+  uint32_t* pk = wst;  // the packed datastore rows, until the window rows are written (fo_lds_bytes)
+  uint2* ist = reinterpret_cast<uint2*>(fo_items_in_T(S) ? smem + (size_t)F_ROW * Sp * 2   // [16][12] item words
+                                                         : reinterpret_cast<unsigned char*>(wst) + kFoWinBytes);
 #if NMMO_FO_XCD  // 1-D grid, an env's groups back to back on one XCD (agent_obs.h ao_env_group)
   int el, g;
   ao_env_group(p.env_list ? p.n_list : p.n_envs, (p.P + kAoAgents - 1) / kAoAgents, el, g);
@@ -279,6 +313,11 @@ __global__ void __launch_bounds__(64 * kAoWaves) flat_obs_kernel(ObsParams p) {
     my_task = 0, my_prev = -1, my_alive = 0;
     my_z = my_s = 0;
   }
+  uint32_t my_rc;  // its position, row | col << 16 (T's row / column columns are reused below)
+  {
+    const int aj = min(abase + kAoWaves * min(lane, kPerWave - 1), P - 1);
+    my_rc = (uint32_t)(uint16_t)T[F_ROW * Sp + aj] | (uint32_t)(uint16_t)T[F_COL * Sp + aj] << 16;
+  }
 #if NMMO_FO_STAMPS
   wst_[1] = __builtin_amdgcn_s_memtime();
 #endif
@@ -286,7 +325,7 @@ __global__ void __launch_bounds__(64 * kAoWaves) flat_obs_kernel(ObsParams p) {
   uint32_t pr[kAoRows];  // this lane's datastore rows 1 + lane + 64 i
 #pragma unroll
   for (int i = 0; i < kAoRows; i++) pr[i] = pk[lane + 64 * i];
-  uint32_t* visw = visw_all + w * 128;
+  uint32_t* visw = visw_all + w * kFoVisw;
   const uint8_t* wsb = reinterpret_cast<const uint8_t*>(wst);
   const float tickf = (float)p.env[(size_t)e * NMMO_NE + E_TICK];
   const bool exch = (p.systems & NMMO_SYS_ITEM) && (p.systems & NMMO_SYS_EXCHANGE);
@@ -313,22 +352,24 @@ __global__ void __launch_bounds__(64 * kAoWaves) flat_obs_kernel(ObsParams p) {
     img = reinterpret_cast<const uint2*>(p.zext)[((size_t)e * P + aa) * kZext + (lane < 40 ? lane % 10 : 10)];
     pinv = reinterpret_cast<const uint2*>(p.zext)[((size_t)e * P + ai) * kZext + 11 + min(lane, 47) % 12];
   }
-  const int nm = min(max(sg.nm, 0), NMMO_MARKET_ROWS);
+  const int nm = min(max(sg.nm, 0), NMMO_MARKET_ROWS), nst = fo_staged(nm);
   const uint2 lwd = ao_listing_load(p, e, sg);
-  // the listings (ascending row) into LDS ahead of the windows' barrier, which publishes them
-  ao_stage_windows(p, e, g, T, Sp, wst, ist, [&]() {
+  // the listings (ascending row) into LDS ahead of the windows' barrier, which publishes them.
+  // The window rows overwrite pk, and at S = 384 the item words overwrite T's row / column columns:
+  // a barrier after every wave's pr / my_rc loads and the windows' own position reads, ahead of those writes
+  ao_stage_windows<kAoAgents, kFoWinRowBytes / 4>(p, e, g, T, Sp, wst, ist, [&]() {
     if (tid < nm) {
       mpo[tid] = (uint16_t)(it_price(lwd) | ((sg.mv >> 16) & 255) << 8);
-      if (tid < kFoStagedListings) mitem[tid] = lwd;
+      if (tid < nst) mtop[-tid] = lwd;
     }
     for (int j = tid + (int)blockDim.x; j < nm; j += blockDim.x) {  // (more listings than threads)
       const int v = p.mlist[(size_t)e * NMMO_MARKET_ROWS + j];
       const int own = (v >> 16) & 255, slot = (v >> 24) & 15;
       const uint2 wd = p.items[((size_t)e * P + own) * kInv + slot];
       mpo[j] = (uint16_t)(it_price(wd) | own << 8);
-      if (j < kFoStagedListings) mitem[j] = wd;
+      if (j < nst) mtop[-j] = wd;
     }
-  });
+  }, []() { __syncthreads(); });
 #if NMMO_FO_STAMPS
   wst_[2] = __builtin_amdgcn_s_memtime();
 #endif
@@ -342,7 +383,7 @@ __global__ void __launch_bounds__(64 * kAoWaves) flat_obs_kernel(ObsParams p) {
   int nrows = 0;                  // rows this wave wrote (rows_out[0])
   unsigned long long nbytes = 0;  // bytes this wave stored (rows_out[1])
   int wo[2];
-  ao_win_offsets(wo);
+  ao_win_offsets<kFoWinRowBytes>(wo);
   int toff[4];  // window tile lane + 64 i: (row offset) & 255 | (col offset) << 8
 #pragma unroll
   for (int i = 0; i < 4; i++) {
@@ -406,11 +447,11 @@ __global__ void __launch_bounds__(64 * kAoWaves) flat_obs_kernel(ObsParams p) {
 #endif
     FO_STAMP(0);
     const int la = a - g * kAoAgents;
-    const int r = __builtin_amdgcn_readfirstlane(T[F_ROW * Sp + a]);
-    const int c = __builtin_amdgcn_readfirstlane(T[F_COL * Sp + a]);
+    const int rcj = __builtin_amdgcn_readlane((int)my_rc, j);
+    const int r = (int16_t)(rcj & 0xFFFF), c = rcj >> 16;
     const int gold = __builtin_amdgcn_readfirstlane(T[F_GOLD * Sp + a]);
     const int aid = __builtin_amdgcn_readfirstlane(T[F_ID * Sp + a]);
-    const uint8_t* wa = wsb + la * kAoWinAgentBytes + ((c - kVision) & 3);
+    const uint8_t* wa = wsb + la * kFoWinAgentBytes;  // (rows realigned while staging: no column term)
     uint32_t wm[4];
 #pragma unroll
     for (int i = 0; i < 4; i++) wm[i] = lane + 64 * i < 225 ? wa[ao_win_off(wo, i)] : 0u;
@@ -478,11 +519,21 @@ __global__ void __launch_bounds__(64 * kAoWaves) flat_obs_kernel(ObsParams p) {
     const int nv2 = (nv + 1) & ~1;
     if (!(NMMO_FO_ABL & 2)) {
       const uint32_t de = kFoEntity + (lane - eh);
+      // the row / column lanes take the packed word's fields (their columns of T hold the item words)
+      const bool epos = (lane & 31) == F_ROW || (lane & 31) == F_COL;
+      const uint32_t esh = (lane & 31) == F_COL ? 16u : 0u;
 #pragma unroll 1
       for (int k0 = 0; k0 < nv2; k0 += 2) {
         const int k = k0 + eh;
-        if (ef < NMMO_N_ENTITY_COLS)
-          fo_st(row, de + k0 * NMMO_N_ENTITY_COLS, k < nv ? (float)T[ef * Sp + ao_slot(visw[k])] : 0.f);
+        if (ef < NMMO_N_ENTITY_COLS) {
+          float v = 0.f;
+          if (k < nv) {
+            const uint32_t vw = visw[k];
+            const int tv = T[ef * Sp + ao_slot(vw)];
+            v = (float)(epos ? (int)((vw >> esh) & 255u) : tv);
+          }
+          fo_st(row, de + k0 * NMMO_N_ENTITY_COLS, v);
+        }
       }
       const int hz = max(nv2, hv);
       wave_zero(row, kFoEntity + nv2 * NMMO_N_ENTITY_COLS, kFoEntity + hz * NMMO_N_ENTITY_COLS);
@@ -509,8 +560,8 @@ __global__ void __launch_bounds__(64 * kAoWaves) flat_obs_kernel(ObsParams p) {
     // (the listings past the staged ones in a loop of their own: a global load in the common loop
     // made every iteration wait for all of the row's stores -- vmcnt counts stores and retires in
     // order -- whether or not it took the load)
-    const int nms = (NMMO_FO_ABL & 8) ? 0 : min(nm, kFoStagedListings);
-    for (int k = lane; k < nms * 16; k += 64) fo_st(row, kFoMarket + k, ic_value(mitem[k >> 4], (mpo[k >> 4] >> 8) + 1, icd));
+    const int nms = (NMMO_FO_ABL & 8) ? 0 : fo_staged(nm);
+    for (int k = lane; k < nms * 16; k += 64) fo_st(row, kFoMarket + k, ic_value(mtop[-(k >> 4)], (mpo[k >> 4] >> 8) + 1, icd));
     if (nm > nms && !(NMMO_FO_ABL & 8)) {
       for (int k = nms * 16 + lane; k < nm * 16; k += 64) {
         const int q = k >> 4;

@@ -1,5 +1,5 @@
 """Diagnostic: market listings per env (rows of the flat obs' Market section) in the C4 bench
-workload, after the staggered pre-roll: how often an env has more than the flat kernel's 256
+workload, after the staggered pre-roll: how often an env has more than the flat kernel's 64
 staged listings (the rest are read from HBM inside the row loop)."""
 import os
 import sys
@@ -32,7 +32,7 @@ def main():
             nm = (m[..., 1] != 0).sum(2).max(1).values.float()
             q = torch.quantile(nm, torch.tensor([0.5, 0.9, 0.99, 1.0], device=dev))
             print(f"tick {t}: listings per env median {q[0]:.0f} p90 {q[1]:.0f} p99 {q[2]:.0f} max {q[3]:.0f}; "
-                  f"envs over 256: {(nm > 256).float().mean().item():.3f}")
+                  f"envs over 64: {(nm > 64).float().mean().item():.3f}")
     eng.close()
 
 

@@ -2,9 +2,12 @@
 // Launches 256 x k workgroups that each spin ~20 us; the launch takes ~one spin per round, so
 // the time jumps when k exceeds the resident workgroups per CU.
 //   hipcc --offload-arch=gfx950 -O3 tools/occupancy_probe.hip -o /tmp/occ && /tmp/occ
+//   /tmp/occ 256 31936 32256 32768     (threads per workgroup, then the LDS sizes to try)
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
+#include <cstdlib>
+#include <vector>
 
 __global__ void spin(float* out, int iters) {
   extern __shared__ float lds[];
@@ -15,17 +18,24 @@ __global__ void spin(float* out, int iters) {
   if (threadIdx.x == 0) out[blockIdx.x] = lds[(threadIdx.x + 1) % blockDim.x];
 }
 
-int main() {
+int main(int argc, char** argv) {
   float* out;
   if (hipMalloc(&out, 4 * 4096 * sizeof(float)) != hipSuccess) return 1;
-  for (int lds : {0}) hipFuncSetAttribute((const void*)spin, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  hipFuncSetAttribute((const void*)spin, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   hipEvent_t t0, t1;
   hipEventCreate(&t0);
   hipEventCreate(&t1);
-  const int threads = 384, iters = 20000;
-  for (int lds : {20480, 32768, 39936, 40448, 40768, 40960, 41984, 53248}) {
+  const int threads = argc > 1 ? atoi(argv[1]) : 384, iters = 20000;
+  std::vector<int> sizes = {20480, 32768, 39936, 40448, 40768, 40960, 41984, 53248};
+  if (argc > 2) {
+    sizes.clear();
+    for (int i = 2; i < argc; i++) sizes.push_back(atoi(argv[i]));
+  }
+  if (threads < 64 || threads > 1024) return 2;
+  for (int lds : sizes) {
+    if (lds < threads * 4 || lds > 160 * 1024) return 2;
     printf("LDS %6d B:", lds);
-    for (int k : {2, 3, 4, 5}) {
+    for (int k : {2, 3, 4, 5, 6}) {
       spin<<<256 * k, threads, lds>>>(out, iters);
       hipEventRecord(t0);
       spin<<<256 * k, threads, lds>>>(out, iters);
