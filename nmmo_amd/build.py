@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(LIB_DIR, "libnmmo_hip.so")
 STAMPS_PATH = os.path.join(LIB_DIR, "libnmmo_hip_stamps.so")
 SOURCES = ["mapgen.hip", "tick.hip", "obs.hip", "wrap.hip", "storage.hip", "wire.hip", "wire_obs.hip", "native_obs.hip",
            "flat_obs.hip", "p2p.hip", "capi.hip"]
-HEADERS = ["agent_obs.h", "common.h", "kernels.h", "wire.h"]
+HEADERS = ["agent_obs.h", "common.h", "kernels.h", "obs_layout.h", "wire.h"]
 ARCH = os.environ.get("NMMO_OFFLOAD_ARCH", "gfx950")
 # the fused action heads (include/nmmo_heads.h): a library of their own, so libnmmo_hip.so's
 # exports, SOURCES / HEADERS and source_hash() stay what the C-ABI tests and bench.py pin

@@ -12,7 +12,7 @@
 //    tested with 16-bit packed math (row and col in the word's two halves);
 //  - the ActionTargets sections are wave-uniform bit fields (ballots over the visible rows and the
 //    12 inventory slots, closed forms for Style / GoldPrice / Move / SellPrice) placed into a bit
-//    image with compile-time shifts (the sections' sizes are nmmo_layout's fixed dims).
+//    image with compile-time shifts (the sections' sizes and offsets: obs_layout.h).
 #pragma once
 
 #include <utility>
@@ -56,25 +56,6 @@ __device__ __forceinline__ bool ao_in_window(uint32_t w, uint32_t rc) {
   return (d.x > d.y ? d.x : d.y) <= 2 * kVision;
 }
 static_assert(kMaxSlots <= 512 && kSize <= 255, "packed entity word");
-
-// The 12 ActionTargets sections (nmmo_layout's dims, flat order) and their flat entry offsets
-// (sec_wire: offsets with Buy.MarketItem left out). Launchers check a handle's layout against
-// sec_flat.
-constexpr int kSecN[12] = {3, 101, NMMO_MARKET_ROWS + 1, kInv + 1, kInv + 1, kNObs + 1, 99, kNObs + 1, 5, kInv + 1, 99, kInv + 1};
-__host__ __device__ constexpr int sec_flat(int k) { return k == 0 ? 0 : sec_flat(k - 1) + kSecN[k - 1]; }
-__host__ __device__ constexpr int sec_wire(int k) { return k < 2 ? sec_flat(k) : sec_flat(k) - kWireBuyN; }
-static_assert(sec_flat(2) == kWireBuyLo && sec_flat(12) == kMaskN && sec_flat(1) == kMkAttackT &&
-                  sec_flat(3) == kMkDestroy && sec_flat(4) == kMkGiveI && sec_flat(5) == kMkGiveT &&
-                  sec_flat(6) == kMkGoldP && sec_flat(7) == kMkGoldT && sec_flat(8) == kMkMove &&
-                  sec_flat(9) == kMkSellI && sec_flat(10) == kMkSellP && sec_flat(11) == kMkUse,
-              "sections (wire.h)");
-__host__ inline bool ao_layout_ok(const ObsParams& p) {
-  const int offs[12] = {p.o_style, p.o_target, p.o_buy, p.o_destroy, p.o_give_item, p.o_give_target,
-                        p.o_gg_price, p.o_gg_target, p.o_move, p.o_sell_item, p.o_sell_price, p.o_use};
-  for (int k = 0; k < 12; k++)
-    if (offs[k] != sec_flat(k)) return false;
-  return p.o_agent_id == sec_flat(12);
-}
 
 // The lane index, opaque to the optimiser: per-lane predicates built from it are recomputed where
 // they are used instead of hoisted out of the agent loops as lane masks (an SGPR pair each), which
@@ -206,27 +187,6 @@ __device__ __forceinline__ uint2 ao_listing_load(const ObsParams& p, int e, cons
   return p.items[((size_t)e * p.P + own) * kInv + slot];
 }
 
-// Workgroup -> (env, agent group) for a 1-D grid of n_envs * G workgroups. Workgroups are
-// dispatched round-robin over the 8 XCDs (id % 8), each with its own L2: the G groups of an env
-// go to one XCD back to back, so the env's staged columns come from HBM once and from that L2
-// G - 1 times (with a 2-D grid an env's groups were n_envs workgroups apart: every group fetched
-// them from HBM). Falls back to adjacent ids when n_envs % 8 != 0. Used by the wire kernel (same
-// box: C5 at N = 1 375 -> 380 M) and the flat kernel (round 6: C4 308 -> 312 M same box, the
-// kernel alone 1 % slower but the overlapped tick gets the HBM reads it no longer makes); the
-// native kernel measured slower with it (round 6 again: C4-native 341 -> 339 M) and keeps the 2-D
-// grid.
-__device__ __forceinline__ void ao_env_group(int n_envs, int G, int& e, int& g) {
-  const int id = blockIdx.x;
-  if ((n_envs & 7) == 0) {
-    const int x = id & 7, q = id >> 3;
-    g = q % G;
-    e = (q / G) * 8 + x;
-  } else {
-    e = id / G;
-    g = id - e * G;
-  }
-}
-
 // The window rows and item words of a workgroup's kAoAgents agents (g * kAoAgents ..), staged in
 // LDS once per workgroup (every thread; one barrier inside): ws[(la * 15 + row) * 5 + k] = the 5
 // aligned dwords holding window row `row` of agent la (its 15 materials start at byte
@@ -329,18 +289,6 @@ __device__ __forceinline__ void ao_window_offsets(int (&mo)[2]) {
 }
 __device__ __forceinline__ int ao_window_off(const int (&mo)[2], int i) {
   return (int)(int16_t)(uint16_t)((uint32_t)mo[i >> 1] >> (16 * (i & 1)));
-}
-
-// Passability of the 5 Move targets from the window materials (tile t in lane t & 63 of wm[t >> 6];
-// the centre's 4 neighbours are all in wm[1])
-__device__ __forceinline__ uint32_t ao_move_bits(uint32_t wm1) {
-  uint32_t b = 0u;
-#pragma unroll
-  for (int d = 0; d < 5; d++) {
-    const int t = (kVision + dir_dr(d)) * 15 + kVision + dir_dc(d);
-    if (!impassable((int)__builtin_amdgcn_readlane((int)wm1, t - 64))) b |= 1u << d;
-  }
-  return b;
 }
 
 // Use.InventoryItem over the inventory (lane k holds slot k's item word; `have`: slot k occupied):

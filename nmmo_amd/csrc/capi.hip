@@ -152,30 +152,27 @@ void nmmo_default_config(NmmoConfig* c) {
 int nmmo_layout(const NmmoConfig* cfg, NmmoLayout* L) {
   if (!cfg || !L) return fail(NMMO_E_INVALID, "null argument");
   memset(L, 0, sizeof(*L));
-  const int dims[NMMO_N_ACTION_HEADS] = {3, 101, 1025, 13, 13, 101, 99, 101, 5, 13, 99, 13};
   L->act_heads = NMMO_N_ACTION_HEADS;
-  int o = 0;
   int* offs[NMMO_N_ACTION_HEADS] = {
       &L->off_mask_attack_style, &L->off_mask_attack_target, &L->off_mask_buy,
       &L->off_mask_destroy, &L->off_mask_give_item, &L->off_mask_give_target,
       &L->off_mask_givegold_price, &L->off_mask_givegold_target, &L->off_mask_move,
       &L->off_mask_sell_item, &L->off_mask_sell_price, &L->off_mask_use};
-  for (int h = 0; h < NMMO_N_ACTION_HEADS; h++) {
-    L->act_dims[h] = dims[h];
-    *offs[h] = o;
-    o += dims[h];
+  for (int h = 0; h < NMMO_N_ACTION_HEADS; h++) {  // obs_layout.h owns the numbers
+    L->act_dims[h] = kSecN[h];
+    *offs[h] = sec_flat(h);
   }
-  L->off_agent_id = o; o += 1;
-  L->off_current_tick = o; o += 1;
-  L->off_entity = o; o += 100 * NMMO_N_ENTITY_COLS;
-  L->off_inventory = o; o += 12 * 16;
-  L->off_market = o; o += 1024 * 16;
-  L->off_task = o; o += cfg->task_embed_dim;
-  L->off_tile = o; o += 225 * 3;
-  L->obs_elems = o;
-  L->entity_rows = 100; L->entity_cols = NMMO_N_ENTITY_COLS;
-  L->inventory_rows = 12; L->item_cols = 16; L->market_rows = 1024;
-  L->tile_rows = 225; L->tile_cols = 3;
+  L->off_agent_id = kFlatId;
+  L->off_current_tick = kFlatTick;
+  L->off_entity = kFlatEntity;
+  L->off_inventory = kFlatInv;
+  L->off_market = kFlatMarket;
+  L->off_task = kFlatTask;
+  L->off_tile = flat_tile(cfg->task_embed_dim);
+  L->obs_elems = flat_elems(cfg->task_embed_dim);
+  L->entity_rows = kNObs; L->entity_cols = NMMO_N_ENTITY_COLS;
+  L->inventory_rows = kInv; L->item_cols = kItemCols; L->market_rows = NMMO_MARKET_ROWS;
+  L->tile_rows = kWinTiles; L->tile_cols = kTileCols;
   const int npc = (cfg->systems & NMMO_SYS_NPC) ? cfg->npc_n : 0;
   L->slots = cfg->player_n + npc;
   L->nf = NMMO_NF;
@@ -297,7 +294,6 @@ int nmmo_create(const NmmoConfig* cfg, int32_t n_envs, uint64_t seed, int32_t de
 }
 
 static ObsParams obs_params(NmmoHandle* h, void* obs) {
-  const NmmoLayout& L = h->layout;
   ObsParams p;
   const bool native = h->cfg.obs_layout == NMMO_OBS_NATIVE, wire = h->cfg.obs_layout == NMMO_OBS_WIRE;
   p.env = h->d_env; p.ent = h->d_ent; p.mat = h->d_mat; p.task = h->d_task;
@@ -305,18 +301,9 @@ static ObsParams obs_params(NmmoHandle* h, void* obs) {
   p.nat = native ? (uint8_t*)obs : nullptr;
   p.wire = wire ? (uint8_t*)obs : nullptr;
   p.items = h->d_items; p.mlist = h->d_mlist; p.mcount = h->d_mcount; p.assign = h->d_assign;
-  p.n_envs = h->st.n_envs; p.P = h->st.P; p.S = h->st.S; p.elems = L.obs_elems;
+  p.n_envs = h->st.n_envs; p.P = h->st.P; p.S = h->st.S;
   p.task_dim = h->cfg.task_embed_dim; p.systems = h->cfg.systems;
   p.spawn_immunity = h->cfg.spawn_immunity;
-  p.o_style = L.off_mask_attack_style; p.o_target = L.off_mask_attack_target;
-  p.o_buy = L.off_mask_buy; p.o_destroy = L.off_mask_destroy;
-  p.o_give_item = L.off_mask_give_item; p.o_give_target = L.off_mask_give_target;
-  p.o_gg_price = L.off_mask_givegold_price; p.o_gg_target = L.off_mask_givegold_target;
-  p.o_move = L.off_mask_move; p.o_sell_item = L.off_mask_sell_item;
-  p.o_sell_price = L.off_mask_sell_price; p.o_use = L.off_mask_use;
-  p.o_agent_id = L.off_agent_id; p.o_tick = L.off_current_tick; p.o_entity = L.off_entity;
-  p.o_inventory = L.off_inventory; p.o_market = L.off_market; p.o_task = L.off_task;
-  p.o_tile = L.off_tile;
   p.row_map = nullptr;
   p.env_list = nullptr;
   p.n_list = 0;

@@ -54,12 +54,12 @@ constexpr int kFoTaskBatch = NMMO_FO_TASK_BATCH;  // Task floats per lane loaded
 constexpr int kFoStagedListings = 64;   // listings whose item words are staged at the least (fo_staged)
 constexpr int kFoChunks = 25;           // 64-entry chunks over the 1,586 mask entries (+ id, tick)
 static_assert(kFoChunks * 64 >= kMaskN + 2 && (kFoChunks - 1) * 64 < kMaskN, "mask chunks");
-static_assert(sec_flat(2) == 104 && sec_flat(3) == 104 + NMMO_MARKET_ROWS + 1, "Buy.MarketItem bits");
-constexpr int kFoBuyLo = sec_flat(2);
-// the flat row's section offsets (nmmo_layout; launch_flat_obs checks the handle's): compile-time,
-// so the agent loop keeps few uniform values live (every runtime offset was an SGPR the loop spilled)
-constexpr int kFoId = kMaskN, kFoEntity = kFoId + 2, kFoInv = kFoEntity + kNObs * NMMO_N_ENTITY_COLS,
-              kFoMarket = kFoInv + kInv * 16, kFoTask = kFoMarket + NMMO_MARKET_ROWS * 16;
+// AgentId and CurrentTick ride in the last chunk right after the mask entries; chunks 2..16 hold
+// only Buy.MarketItem entries (fo_slot)
+static_assert(kFlatId == kMaskN && kFlatTick == kMaskN + 1 && kFlatEntity == kMaskN + 2, "id, tick in the last chunk");
+static_assert(kWireBuyLo / 64 == 1 && (kWireBuyLo + NMMO_MARKET_ROWS) / 64 == 17, "Buy.MarketItem: chunks 1 to 17");
+// (the flat row's section offsets are compile-time, obs_layout.h: every runtime offset was an SGPR
+// the agent loop spilled)
 
 // LDS: agent_obs.h's Entity columns T | the listings' pool | per-wave visible rows | the workgroup's
 // staged window rows (16 B each, realigned) | its item words. 31,936 B at S = 384: 5 workgroups per
@@ -145,7 +145,7 @@ __device__ __forceinline__ void fo_st(float* row, uint32_t idx, float v) {
 // AgentId, CurrentTick) as slots 0..9. A chunk whose mask equals the one the row was last written
 // with is not stored again: per tick an agent's Move and Attack.Target bits change, while the
 // gold-, inventory- and same-tile-driven sections mostly do not.
-constexpr int kFoTail0 = (kFoBuyLo + NMMO_MARKET_ROWS) / 64;  // 17
+constexpr int kFoTail0 = (kWireBuyLo + NMMO_MARKET_ROWS) / 64;  // 17
 __host__ __device__ constexpr int fo_slot(int c) { return c < 2 ? c : c - kFoTail0 + 2; }
 static_assert(fo_slot(kFoChunks - 1) == 9 && kZext == 10 + 1 + 12, "tracked chunks | position | items");
 struct FoImg {
@@ -186,7 +186,7 @@ __device__ __forceinline__ void fo_tail_chunks(float* row, FoImg& g, const AoSec
                                                float tick) {
   if constexpr (kC < kFoChunks) {
     uint64_t m = fo_chunk<kC>(x);
-    if constexpr (kC == kFoTail0) m |= buy17 | 1ull << ((kFoBuyLo + NMMO_MARKET_ROWS) & 63);
+    if constexpr (kC == kFoTail0) m |= buy17 | 1ull << ((kWireBuyLo + NMMO_MARKET_ROWS) & 63);
     fo_put<kC>(row, g, m, aid, tick);
     fo_tail_chunks<kC + 1>(row, g, x, buy17, aid, tick);
   }
@@ -261,7 +261,7 @@ typedef const __attribute__((address_space(4))) ObsParams* FoArgs;  // the kerne
 template <bool kWrap, int kS>
 __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per_eu(5, 5))) flat_obs_kernel(ObsParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int S = kS ? kS : p.S, P = p.P, Sp = ao_stride(S), tdim = p.task_dim, elems = kFoTask + tdim + 225 * 3;
+  const int S = kS ? kS : p.S, P = p.P, Sp = ao_stride(S), tdim = p.task_dim, elems = kFlatTask + tdim + kTileN;
   int16_t* T = reinterpret_cast<int16_t*>(smem);
   uint16_t* mpo = reinterpret_cast<uint16_t*>(smem + ao_columns_lds(S));       // [1024] price | owner << 8
   uint32_t* visw_all = reinterpret_cast<uint32_t*>(mpo) + kFoListPool / 4;       // [4][100]
@@ -418,18 +418,18 @@ __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per
     if (!__builtin_amdgcn_readlane(my_alive, j)) {  // not in the realm: an all-zero row
       if ((zzero >> j) & 1) {  // zeroed by an earlier launch into this buffer
         if ((ztile >> j) & 1) {  // ... but a consumer wrote into its Tile section since
-          wave_zero(row, kFoTask + tdim, elems);
-          nbytes += 4ull * (elems - kFoTask - tdim);
+          wave_zero(row, kFlatTask + tdim, elems);
+          nbytes += 4ull * (elems - kFlatTask - tdim);
           if (lane == 0) kp->zst[(size_t)e * P + a] = kZsZero;
           nrows++;
         }
         continue;
       }
       if (zv) {  // zero what the last write left nonzero
-        wave_zero(row, 0, kFoEntity + hv * NMMO_N_ENTITY_COLS);
-        wave_zero(row, kFoInv, kFoMarket + hm * 16);
-        wave_zero(row, kFoTask, elems);
-        nbytes += 4ull * (kFoEntity + hv * NMMO_N_ENTITY_COLS + kFoMarket + hm * 16 - kFoInv + elems - kFoTask);
+        wave_zero(row, 0, kFlatEntity + hv * NMMO_N_ENTITY_COLS);
+        wave_zero(row, kFlatInv, kFlatMarket + hm * 16);
+        wave_zero(row, kFlatTask, elems);
+        nbytes += 4ull * (kFlatEntity + hv * NMMO_N_ENTITY_COLS + kFlatMarket + hm * 16 - kFlatInv + elems - kFlatTask);
       } else {
         wave_zero(row, 0, elems);
         nbytes += 4ull * elems;
@@ -497,19 +497,19 @@ __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per
         return __ballot(bv);
       };
       const int nbuy = max(nm, hm);
-      const int clast = max(1, min((kFoBuyLo + nbuy - 1) >> 6, 16));
+      const int clast = max(1, min((kWireBuyLo + nbuy - 1) >> 6, 16));
       uint64_t bprev = nm > 0 ? buy_word(0) : 0ull;  // chunk 1: Attack.Target's tail, Buy's first 24
-      fo_put<1>(row, fg, fo_chunk<1>(x) | bprev << (kFoBuyLo & 63), 0.f, 0.f);
+      fo_put<1>(row, fg, fo_chunk<1>(x) | bprev << (kWireBuyLo & 63), 0.f, 0.f);
       FO_STAMP(3);
 #pragma unroll 1
       for (int cc = 2; cc <= clast; cc++) {  // Buy-only chunks, not tracked
         const uint64_t bcur = 64 * (cc - 1) < nm ? buy_word(cc - 1) : 0ull;
-        fo_st(row, 64 * cc + lane, fo_bit(bcur << (kFoBuyLo & 63) | bprev >> (64 - (kFoBuyLo & 63))));
+        fo_st(row, 64 * cc + lane, fo_bit(bcur << (kWireBuyLo & 63) | bprev >> (64 - (kWireBuyLo & 63))));
         bprev = bcur;
       }
       // chunk 17: Buy entries 984..1023 (word 15, only when nm > 960: the loop then ran to 16)
       FO_STAMP(4);
-      const uint64_t buy17 = nm > 15 * 64 ? bprev >> (64 - (kFoBuyLo & 63)) : 0ull;
+      const uint64_t buy17 = nm > 15 * 64 ? bprev >> (64 - (kWireBuyLo & 63)) : 0ull;
       fo_tail_chunks<kFoTail0>(row, fg, x, buy17, (float)aid, tickf);
       nbytes += 4ull * (fg.nst + 64 * (clast - 1));
     }
@@ -518,7 +518,7 @@ __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per
     // the rows past the visible ones not known zero as one zero run
     const int nv2 = (nv + 1) & ~1;
     if (!(NMMO_FO_ABL & 2)) {
-      const uint32_t de = kFoEntity + (lane - eh);
+      const uint32_t de = kFlatEntity + (lane - eh);
       // the row / column lanes take the packed word's fields (their columns of T hold the item words)
       const bool epos = (lane & 31) == F_ROW || (lane & 31) == F_COL;
       const uint32_t esh = (lane & 31) == F_COL ? 16u : 0u;
@@ -536,7 +536,7 @@ __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per
         }
       }
       const int hz = max(nv2, hv);
-      wave_zero(row, kFoEntity + nv2 * NMMO_N_ENTITY_COLS, kFoEntity + hz * NMMO_N_ENTITY_COLS);
+      wave_zero(row, kFlatEntity + nv2 * NMMO_N_ENTITY_COLS, kFlatEntity + hz * NMMO_N_ENTITY_COLS);
       nbytes += 4ull * (hz * NMMO_N_ENTITY_COLS + max(nm, hm) * 16);
     }
     FO_STAMP(6);
@@ -551,7 +551,7 @@ __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per
         const int q = 4 * h + iq;
         float v = 0.f;
         if (4 * h < ninv && q < ninv) v = ic_value(ist[la * kInv + q], aid, icd);  // (a uniform skip first)
-        fo_st(row, kFoInv + 64 * h + lane, v);
+        fo_st(row, kFlatInv + 64 * h + lane, v);
       }
       nbytes += 4ull * kInv * 16;
     }
@@ -561,16 +561,16 @@ __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per
     // made every iteration wait for all of the row's stores -- vmcnt counts stores and retires in
     // order -- whether or not it took the load)
     const int nms = (NMMO_FO_ABL & 8) ? 0 : fo_staged(nm);
-    for (int k = lane; k < nms * 16; k += 64) fo_st(row, kFoMarket + k, ic_value(mtop[-(k >> 4)], (mpo[k >> 4] >> 8) + 1, icd));
+    for (int k = lane; k < nms * 16; k += 64) fo_st(row, kFlatMarket + k, ic_value(mtop[-(k >> 4)], (mpo[k >> 4] >> 8) + 1, icd));
     if (nm > nms && !(NMMO_FO_ABL & 8)) {
       for (int k = nms * 16 + lane; k < nm * 16; k += 64) {
         const int q = k >> 4;
         const int v = kp->mlist[(size_t)e * NMMO_MARKET_ROWS + q];
         const uint2 wd = kp->items[((size_t)e * P + ((v >> 16) & 255)) * kInv + ((v >> 24) & 15)];
-        fo_st(row, kFoMarket + k, ic_value(wd, (mpo[q] >> 8) + 1, icd));
+        fo_st(row, kFlatMarket + k, ic_value(wd, (mpo[q] >> 8) + 1, icd));
       }
     }
-    wave_zero(row, kFoMarket + nm * 16, kFoMarket + max(nm, hm) * 16);
+    wave_zero(row, kFlatMarket + nm * 16, kFlatMarket + max(nm, hm) * 16);
     FO_STAMP(8);
     // Task: only when the row does not hold this task's embedding yet (read in place)
     const int task = __builtin_amdgcn_readlane(my_task, j);
@@ -584,9 +584,9 @@ __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per
 #pragma unroll
         for (int i = 0; i < kFoTaskBatch; i++) t[i] = temb[k0 + 64 * i + lane];
 #pragma unroll
-        for (int i = 0; i < kFoTaskBatch; i++) fo_st(row, kFoTask + k0 + 64 * i + lane, t[i]);
+        for (int i = 0; i < kFoTaskBatch; i++) fo_st(row, kFlatTask + k0 + 64 * i + lane, t[i]);
       }
-      for (int k = k0 + lane; k < tdim; k += 64) fo_st(row, kFoTask + k, temb[k]);
+      for (int k = k0 + lane; k < tdim; k += 64) fo_st(row, kFlatTask + k, temb[k]);
       nbytes += 4ull * tdim;
     }
     FO_STAMP(9);
@@ -599,7 +599,7 @@ __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per
     const bool tkn = NMMO_FO_TILE_SKIP && ext && !((ztile >> j) & 1);  // the Tile section holds what this kernel wrote
     const bool same_r = tkn && (int)(ppos & 255u) == r, same_c = tkn && (int)((ppos >> 8) & 255u) == c;
     if (!(NMMO_FO_ABL & 16)) {
-      float* dt = row + kFoTask + tdim + 3 * lane;
+      float* dt = row + kFlatTask + tdim + 3 * lane;
 #pragma unroll
       for (int i = 0; i < 4; i++) {
         if (lane + 64 * i < 225) {
@@ -655,10 +655,7 @@ __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per
 }
 
 bool flat_obs_ok(const ObsParams& p) {  // agent_obs.h's staging: S a multiple of 8 (16-B column loads)
-  return p.S % 8 == 0 && p.S <= kMaxSlots && p.P <= 128 && p.obs && p.ztag && p.zrow && ao_layout_ok(p) &&
-         p.o_agent_id == kFoId && p.o_tick == kFoId + 1 && p.o_entity == kFoEntity && p.o_inventory == kFoInv &&
-         p.o_market == kFoMarket && p.o_task == kFoTask && p.o_tile == kFoTask + p.task_dim &&
-         p.elems == p.o_tile + 225 * 3;
+  return p.S % 8 == 0 && p.S <= kMaxSlots && p.P <= 128 && p.obs && p.ztag && p.zrow;
 }
 
 hipError_t launch_flat_obs(const ObsParams& p, hipStream_t stream) {

@@ -2,6 +2,7 @@
 #pragma once
 
 #include "common.h"
+#include "obs_layout.h"
 
 namespace nmmo {
 
@@ -78,18 +79,16 @@ struct ObsParams {
   const int* mcount;    // [n]
   const float* task;    // [n_tasks][task_dim] Task obs per task
   const int32_t* assign; // [n][P]
-  float* obs;           // [n][P][elems] (flat layout)
+  float* obs;           // [n][P][flat_elems(task_dim)] (flat layout, obs_layout.h)
   uint8_t* nat;         // native layout (SPEC §8b) instead of obs when non-NULL
   uint8_t* wire;        // wire layout (SPEC §8c, NMMO_OBS_WIRE) instead of obs / nat when non-NULL;
                         // expand: the wire buffer the flat rows are decoded from
   const int* row_map;   // expand only: flat row of agent row e*P+a (< 0 = skip); NULL = identity
-  int n_envs, P, S, elems, task_dim;
+  // task_dim: the layout's one run-time value (obs_layout.h flat_tile / flat_elems). counted (wire
+  // layout): the tick wrote the header's count words (DevState::wf), no count launch
+  int n_envs, P, S, counted, task_dim;
   uint32_t systems;
   int spawn_immunity;
-  // flat offsets (NmmoLayout)
-  int o_style, o_target, o_buy, o_destroy, o_give_item, o_give_target, o_gg_price, o_gg_target,
-      o_move, o_sell_item, o_sell_price, o_use, o_agent_id, o_tick, o_entity, o_inventory,
-      o_market, o_task, o_tile;
   // wrapper observation edits (SPEC §13): kWrapObs* bits, prev_price from the wrapper state
   const NmmoWrapState* ws;  // [n][P] or NULL
   int wflags;
@@ -125,7 +124,6 @@ struct ObsParams {
   const uint8_t* trunc;
   const uint8_t* mask;
   unsigned long long* rows_out;  // optional [n][2]: += rows this launch wrote, bytes it stored, per env
-  int counted;  // wire layout: the tick wrote the header's count words (DevState::wf), no count launch
 };
 constexpr uint64_t kZsZero = 1ull << 20;
 constexpr uint64_t kZsExt = 1ull << 21;  // the row's extended state (ObsParams::zext) is valid
@@ -144,6 +142,39 @@ __device__ __forceinline__ uint64_t readlane_u64(uint64_t v, int j) {
          (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), j) << 32;
 }
 constexpr int kWrapObsPrice = 1, kWrapObsNoGive = 2, kWrapObsNoDangerous = 4;
+
+// Pieces the obs kernels of every layout share (obs.hip, agent_obs.h).
+// Workgroup -> (env, agent group) for a 1-D grid of n_envs * G workgroups. Workgroups are
+// dispatched round-robin over the 8 XCDs (id % 8), each with its own L2: the G groups of an env
+// go to one XCD back to back, so the env's staged columns come from HBM once and from that L2
+// G - 1 times (with a 2-D grid an env's groups were n_envs workgroups apart: every group fetched
+// them from HBM). Falls back to adjacent ids when n_envs % 8 != 0. Used by the wire kernel (same
+// box: C5 at N = 1 375 -> 380 M) and the flat kernel (round 6: C4 308 -> 312 M same box, the
+// kernel alone 1 % slower but the overlapped tick gets the HBM reads it no longer makes); the
+// native kernel measured slower with it (round 6 again: C4-native 341 -> 339 M) and keeps the 2-D
+// grid.
+__device__ __forceinline__ void ao_env_group(int n_envs, int G, int& e, int& g) {
+  const int id = blockIdx.x;
+  if ((n_envs & 7) == 0) {
+    const int x = id & 7, q = id >> 3;
+    g = q % G;
+    e = (q / G) * 8 + x;
+  } else {
+    e = id / G;
+    g = id - e * G;
+  }
+}
+// Passability of the 5 Move targets from the window materials (tile t in lane t & 63 of wm[t >> 6];
+// the centre's 4 neighbours are all in wm[1])
+__device__ __forceinline__ uint32_t ao_move_bits(uint32_t wm1) {
+  uint32_t b = 0u;
+#pragma unroll
+  for (int d = 0; d < 5; d++) {
+    const int t = (kVision + dir_dr(d)) * 15 + kVision + dir_dc(d);
+    if (!impassable((int)__builtin_amdgcn_readlane((int)wm1, t - 64))) b |= 1u << d;
+  }
+  return b;
+}
 
 struct WrapParams {
   const int32_t* env;        // [n][NE]

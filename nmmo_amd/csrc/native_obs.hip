@@ -31,9 +31,8 @@ static_assert(kNoAgents / kNoWaves == kAoAgents / kAoWaves, "agents per wave: ag
 __host__ __device__ inline size_t no_lds_bytes(int S) {
   return ao_entity_lds(S) + (size_t)NMMO_MARKET_ROWS * 2 + (size_t)kNoWaves * 128 * 4 + ao_win_lds(kNoAgents);
 }
-constexpr int kNoEntity = 2, kNoInv = kNoEntity + kNObs * NMMO_N_ENTITY_COLS, kNoTile = kNoInv + kInv * 16,
-              kNoTask = kNoTile + 225 * 3;  // int16 offsets in the int16 part (SPEC §8b)
-static_assert(kNoTask < NMMO_NATIVE_I16 && (kNoTile & 1) == 0 && (NMMO_NATIVE_I16 & 1) == 0 &&
+static_assert(kNatTask < NMMO_NATIVE_I16 && (kNatEntity & 1) == 0 && (kNatInv & 1) == 0 && (kNatTile & 1) == 0 &&
+                  (NMMO_NATIVE_I16 & 1) == 0 &&  // (dword stores into the int16 part)
                   NMMO_NATIVE_MASK_BYTES % 16 == 0 && NMMO_NATIVE_ROW_BYTES % 16 == 0,
               "native layout");
 constexpr int kNoImgWords = NMMO_NATIVE_MASK_BYTES / 32;  // 50: the mask image, one dword per lane
@@ -196,7 +195,7 @@ __global__ void __launch_bounds__(64 * kNoWaves) native_obs_kernel(ObsParams p) 
       ao_image<true>(ao_sections<kWrap>(p, T, Sp, visw, ag, it), img);
       img[(kWireBuyLo + NMMO_MARKET_ROWS) / 32] |= 1u << ((kWireBuyLo + NMMO_MARKET_ROWS) & 31);  // Buy noop
       // the section words (dwords 0-3 and 35-49: Buy.MarketItem fills the ones between)
-      static_assert(sec_flat(2) / 32 == 3 && (sec_flat(3) - 1) / 32 == 35, "Buy.MarketItem dwords");
+      static_assert(kWireBuyLo / 32 == 3 && (kWireBuyLo + kWireBuyN - 1) / 32 == 35, "Buy.MarketItem dwords");
       int x = 0;
       x = writelanes<0, 0, 4>(img, x);
       x = writelanes<35, 35, kNoImgWords - 35>(img, x);
@@ -244,7 +243,7 @@ __global__ void __launch_bounds__(64 * kNoWaves) native_obs_kernel(ObsParams p) 
       const int f0 = c0 - r0 * NMMO_N_ENTITY_COLS, f1 = c1 - r1 * NMMO_N_ENTITY_COLS;
       const int nv4 = (nv + 3) & ~3;
       const int hz = max(nv4, hv);  // the rows past the visible ones not known zero
-      uint32_t* de = d32 + kNoEntity / 2;
+      uint32_t* de = d32 + kNatEntity / 2;
 #pragma unroll 1
       for (int k0 = 0; k0 < nv4; k0 += 4) {
         const int k = k0 + 2 * hp, ka = k + r0, kb = k + r1;
@@ -254,8 +253,8 @@ __global__ void __launch_bounds__(64 * kNoWaves) native_obs_kernel(ObsParams p) 
           de[(k >> 1) * NMMO_N_ENTITY_COLS + i] = i16pack(lo, hi);
         }
       }
-      uint8_t* zb = nrow + NMMO_NATIVE_MASK_BYTES + 2 * (kNoEntity + nv4 * NMMO_N_ENTITY_COLS);
-      uint8_t* ze = nrow + NMMO_NATIVE_MASK_BYTES + 2 * (kNoEntity + hz * NMMO_N_ENTITY_COLS);
+      uint8_t* zb = nrow + NMMO_NATIVE_MASK_BYTES + 2 * (kNatEntity + nv4 * NMMO_N_ENTITY_COLS);
+      uint8_t* ze = nrow + NMMO_NATIVE_MASK_BYTES + 2 * (kNatEntity + hz * NMMO_N_ENTITY_COLS);
       nbytes += NMMO_NATIVE_ROW_BYTES - 2 * (kNObs - hz) * NMMO_N_ENTITY_COLS;
       if (p.ztag && lane == 0) {
         if (!((zvalid >> j) & 1)) p.zrow[(size_t)e * P + a] = p.ztag;
@@ -273,7 +272,7 @@ __global__ void __launch_bounds__(64 * kNoWaves) native_obs_kernel(ObsParams p) 
     }
     // Inventory: 96 dwords (item q = i >> 3, columns 2i & 15, +1), the item word from lane q
     if (ninv == 0) {
-      if (lane < kInv * 8 / 4) reinterpret_cast<uint4*>(d32 + kNoInv / 2)[lane] = make_uint4(0u, 0u, 0u, 0u);
+      if (lane < kInv * 8 / 4) reinterpret_cast<uint4*>(d32 + kNatInv / 2)[lane] = make_uint4(0u, 0u, 0u, 0u);
     } else {
 #pragma unroll
       for (int h = 0; h < 2; h++) {
@@ -282,7 +281,7 @@ __global__ void __launch_bounds__(64 * kNoWaves) native_obs_kernel(ObsParams p) 
         const uint2 iw = make_uint2((uint32_t)__shfl((int)it.x, q), (uint32_t)__shfl((int)it.y, q));
         if (i < kInv * 8) {
           const int cc = (2 * i) & 15;
-          d32[kNoInv / 2 + i] =
+          d32[kNatInv / 2 + i] =
               (i >> 3) < ninv ? i16pack((int)item_col(iw, aid, cc), (int)item_col(iw, aid, cc + 1)) : 0u;
         }
       }
@@ -290,7 +289,7 @@ __global__ void __launch_bounds__(64 * kNoWaves) native_obs_kernel(ObsParams p) 
     // Tile: (row, col, material) per window tile t = lane + 64 i as three int16 stores (the
     // lane's row / column offsets are per-wave constants), then the task index and the zero pad
     {
-      int16_t* d16 = reinterpret_cast<int16_t*>(d32) + kNoTile;
+      int16_t* d16 = reinterpret_cast<int16_t*>(d32) + kNatTile;
 #pragma unroll
       for (int i = 0; i < 4; i++) {
         const int t = lane + 64 * i;
@@ -300,8 +299,8 @@ __global__ void __launch_bounds__(64 * kNoWaves) native_obs_kernel(ObsParams p) 
           d16[3 * t + 2] = (int16_t)wm[i];
         }
       }
-      if (lane < NMMO_NATIVE_I16 - kNoTask)
-        d16[225 * 3 + lane] = lane == 0 ? (int16_t)__builtin_amdgcn_readlane(my_task, j) : (int16_t)0;
+      if (lane < NMMO_NATIVE_I16 - kNatTask)
+        d16[kTileN + lane] = lane == 0 ? (int16_t)__builtin_amdgcn_readlane(my_task, j) : (int16_t)0;
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the next agent reuses visw
     __builtin_amdgcn_wave_barrier();
@@ -314,7 +313,7 @@ __global__ void __launch_bounds__(64 * kNoWaves) native_obs_kernel(ObsParams p) 
 }
 
 hipError_t launch_native_obs(const ObsParams& p, hipStream_t stream) {
-  if (p.S % 8 || p.S > kMaxSlots || p.P > 128 || !p.nat || !ao_layout_ok(p)) return hipErrorInvalidValue;
+  if (p.S % 8 || p.S > kMaxSlots || p.P > 128 || !p.nat) return hipErrorInvalidValue;
   const int ne = list_grid(p.env_list, p.n_list, p.n_envs);
   if (ne <= 0) return hipSuccess;
 #ifdef NMMO_NO_XCD

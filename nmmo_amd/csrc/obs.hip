@@ -56,38 +56,12 @@ __device__ inline void wave_zero_bytes(uint8_t* row, int lo, int hi) {
   if (t0 + 2 * lane < hi) reinterpret_cast<int16_t*>(row + t0)[lane] = 0;
 }
 
-// native layout (SPEC §8b): int16 part offsets, env stride, two int16 per dword store
-constexpr int kNatEntity = 2, kNatInv = kNatEntity + kNObs * NMMO_N_ENTITY_COLS,
-              kNatTile = kNatInv + kInv * 16, kNatTask = kNatTile + 225 * 3;
-static_assert(kNatTask < NMMO_NATIVE_I16, "native int16 part overflows its row");
-__host__ __device__ inline size_t native_env_bytes(int P) {
-  return (size_t)P * NMMO_NATIVE_ROW_BYTES + NMMO_NATIVE_MARKET_BYTES;
-}
-
 // One agent's view for the ActionTargets sections (SPEC §8, §9, §13 edits).
 struct MaskCtx {
   int a, r, c, nv, gold, ninv, prev_price;
   uint32_t movebits;  // bit d: the tile in direction d is passable
   bool combat, item, exch, no_give;
 };
-
-// The 12 ActionTargets sections in flat order: [lo, lo + n) of the mask part of the row.
-__device__ __forceinline__ void mask_section(const ObsParams& p, int sec, int& lo, int& n) {
-  switch (sec) {
-    case 0: lo = p.o_style; n = p.o_target - p.o_style; break;
-    case 1: lo = p.o_target; n = kNObs + 1; break;
-    case 2: lo = p.o_buy; n = NMMO_MARKET_ROWS + 1; break;
-    case 3: lo = p.o_destroy; n = kInv + 1; break;
-    case 4: lo = p.o_give_item; n = kInv + 1; break;
-    case 5: lo = p.o_give_target; n = kNObs + 1; break;
-    case 6: lo = p.o_gg_price; n = p.o_gg_target - p.o_gg_price; break;
-    case 7: lo = p.o_gg_target; n = kNObs + 1; break;
-    case 8: lo = p.o_move; n = p.o_sell_item - p.o_move; break;
-    case 9: lo = p.o_sell_item; n = kInv + 1; break;
-    case 10: lo = p.o_sell_price; n = p.o_use - p.o_sell_price; break;
-    default: lo = p.o_use; n = p.o_agent_id - p.o_use; break;
-  }
-}
 
 // Entry k of section sec (the section id is wave-uniform: no lane evaluates another section's
 // predicate). Buy.MarketItem reads the packed listings (price | owner << 8) in either layout.
@@ -138,29 +112,14 @@ __device__ __forceinline__ bool mask_value(const ObsParams& p, const int16_t* T,
 }
 
 // Section kSec of the ActionTargets as float32 0/1 straight into a flat row: the section is a
-// template constant, so mask_section / mask_value fold to straight-line code (the generic
+// template constant, so its bounds and mask_value fold to straight-line code (the generic
 // (section, chunk) loop spent ~1.3k scalar and branch instructions per agent on the dispatch).
 template <int kSec, bool kWrap>
 __device__ __forceinline__ void mask_sec_f32(const ObsParams& p, const int16_t* T, int S, const int16_t* vis,
                                              const uint2* inv, const uint16_t* mpo, int nm, const MaskCtx& m,
                                              float* row) {
-  int lo, n;
-  mask_section(p, kSec, lo, n);
-  for (int k = lane_id(); k < n; k += 64)
-    obs_st(&row[lo + k], mask_value<kWrap>(p, T, S, vis, inv, mpo, nm, m, kSec, k) ? 1.f : 0.f);
-}
-
-// Passability of the 5 move targets from the prefetched window materials: tile t of the 15x15
-// window sits in lane t & 63 of register t >> 6; the centre's 4 neighbours (t = 97, 111, 112,
-// 113, 127) are all in register 1.
-__device__ __forceinline__ uint32_t move_bits(uint32_t wm1) {
-  uint32_t b = 0u;
-#pragma unroll
-  for (int d = 0; d < 5; d++) {
-    const int t = (kVision + dir_dr(d)) * 15 + kVision + dir_dc(d);
-    if (!impassable((int)__builtin_amdgcn_readlane((int)wm1, t - 64))) b |= 1u << d;
-  }
-  return b;
+  for (int k = lane_id(); k < kSecN[kSec]; k += 64)
+    obs_st(&row[sec_flat(kSec) + k], mask_value<kWrap>(p, T, S, vis, inv, mpo, nm, m, kSec, k) ? 1.f : 0.f);
 }
 
 // Flat rows: each agent's global loads (its 12 item words, 15x15 window materials, Task
@@ -193,7 +152,7 @@ __attribute__((amdgpu_waves_per_eu(kFull ? NMMO_OBS_FULL_WPE : NMMO_OBS_WPE, kFu
 obs_kernel(ObsParams p) {
   constexpr int kTaskRegs = kFull ? kTaskRegsFull : NMMO_OBS_TASK_REGS;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int S = p.S;
+  const int S = p.S, elems = flat_elems(p.task_dim);
   int16_t* T = reinterpret_cast<int16_t*>(smem);
   // datastore row k -> slot | row << 16 | col << 24 of the entity on it (0xFFFFFFFF: none)
   uint32_t* rowpk = reinterpret_cast<uint32_t*>(smem + (((size_t)kObsFields * S * 2 + 15) & ~(size_t)15));
@@ -202,17 +161,9 @@ obs_kernel(ObsParams p) {
   uint2* mitem = inv_all + kFlatWaves * kInv;  // listed item words
   uint16_t* mpo = reinterpret_cast<uint16_t*>(mitem + NMMO_MARKET_ROWS);  // price | owner << 8
   uint8_t* wmat_all = reinterpret_cast<uint8_t*>(mpo + NMMO_MARKET_ROWS);  // per-wave 15x15 materials
-#ifdef NMMO_OBS_XCD  // A/B knob: 1-D grid, an env's groups on one XCD (as agent_obs.h ao_env_group)
-  const int G = (p.P + kFlatAgents - 1) / kFlatAgents, ne = p.env_list ? p.n_list : p.n_envs;
+#ifdef NMMO_OBS_XCD  // A/B knob: 1-D grid, an env's groups on one XCD
   int el, g;
-  if ((ne & 7) == 0) {
-    const int x = blockIdx.x & 7, q = blockIdx.x >> 3;
-    g = q % G;
-    el = (q / G) * 8 + x;
-  } else {
-    el = blockIdx.x / G;
-    g = blockIdx.x - el * G;
-  }
+  ao_env_group(p.env_list ? p.n_list : p.n_envs, (p.P + kFlatAgents - 1) / kFlatAgents, el, g);
   const int e = p.env_list ? p.env_list[el] : el;
 #else
   const int e = p.env_list ? p.env_list[blockIdx.x] : (int)blockIdx.x, g = blockIdx.y;
@@ -335,7 +286,7 @@ obs_kernel(ObsParams p) {
   for (int j = 0; j < kPerWave; j++) {
     const int a = abase + kFlatWaves * j;
     if (a >= p.P) break;
-    float* row = p.obs + ((size_t)e * p.P + a) * p.elems;
+    float* row = p.obs + ((size_t)e * p.P + a) * elems;
     const bool zv = (zvalid >> j) & 1;
     const int hj = __builtin_amdgcn_readlane(my_h, j);
     const int hv = hj & 4095, hm = hj >> 12;
@@ -343,14 +294,14 @@ obs_kernel(ObsParams p) {
       if (alive(j + 1)) prefetch(a + kFlatWaves, j + 1);  // ahead of this row's stores
       if ((zzero >> j) & 1) continue;  // zeroed by an earlier launch into this buffer
       if (zv) {  // zero what the last write left nonzero
-        wave_zero(row, 0, p.o_entity + hv * NMMO_N_ENTITY_COLS);
-        wave_zero(row, p.o_inventory, p.o_market + hm * 16);
-        wave_zero(row, p.o_task, p.elems);
-        nbytes += 4ull * (p.o_entity + hv * NMMO_N_ENTITY_COLS + p.o_market + hm * 16 - p.o_inventory +
-                          p.elems - p.o_task);
+        wave_zero(row, 0, kFlatEntity + hv * NMMO_N_ENTITY_COLS);
+        wave_zero(row, kFlatInv, kFlatMarket + hm * kItemCols);
+        wave_zero(row, kFlatTask, elems);
+        nbytes += 4ull * (kFlatEntity + hv * NMMO_N_ENTITY_COLS + kFlatMarket + hm * kItemCols - kFlatInv +
+                          elems - kFlatTask);
       } else {
-        wave_zero(row, 0, p.elems);
-        nbytes += 4ull * p.elems;
+        wave_zero(row, 0, elems);
+        nbytes += 4ull * elems;
       }
       if (p.ztag && lane == 0) {
         p.zrow[(size_t)e * p.P + a] = p.ztag;
@@ -370,7 +321,7 @@ obs_kernel(ObsParams p) {
 #pragma unroll
     for (int i = 0; i < 4; i++)
       if (lane + 64 * i < 225) wmat[lane + 64 * i] = (uint8_t)wm[i];
-    m.movebits = move_bits(wm[1]);
+    m.movebits = ao_move_bits(wm[1]);
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     // lane-per-tile: three dword stores 12 B apart per window tile (the pass's three stores fill
@@ -380,7 +331,7 @@ obs_kernel(ObsParams p) {
 #pragma unroll 1
     for (int t = lane; t < 225; t += 64) {
       const int tr = (t * 0x1112u) >> 16;  // t / 15 for t < 225
-      float* d = &row[p.o_tile + 3 * t];
+      float* d = &row[flat_tile(p.task_dim) + 3 * t];
       obs_st(&d[0], (float)(m.r + tr - kVision));
       obs_st(&d[1], (float)(m.c + t - 15 * tr - kVision));
       obs_st(&d[2], (float)wmat[t]);
@@ -398,12 +349,12 @@ obs_kernel(ObsParams p) {
       nbytes += 4ull * p.task_dim;
       const int k0 = treg ? kTaskRegs * 64 : 0;  // a shorter embedding is read in place
       if (treg) {
-        float* dst = row + p.o_task + lane;
+        float* dst = row + kFlatTask + lane;
 #pragma unroll
         for (int i = 0; i < kTaskRegs; i++) obs_st(&dst[64 * i], tv[i]);
       }
       const float* temb = p.task + (size_t)__builtin_amdgcn_readlane(my_task, j) * p.task_dim;
-      for (int k = k0 + lane; k < p.task_dim; k += 64) obs_st(&row[p.o_task + k], temb[k]);
+      for (int k = k0 + lane; k < p.task_dim; k += 64) obs_st(&row[kFlatTask + k], temb[k]);
     }
     // the next agent's loads go out now, ahead of this row's remaining stores
     if (alive(j + 1)) prefetch(a + kFlatWaves, j + 1);
@@ -413,9 +364,9 @@ obs_kernel(ObsParams p) {
     {  // Buy.MarketItem: the listings' entries, the zero entries up to hm, and the no-op entry
       const int n = max(nm, hm);
       for (int k = lane; k < n; k += 64)
-        obs_st(&row[p.o_buy + k], mask_value<kWrap>(p, T, S, vis, inv, mpo, nm, m, 2, k) ? 1.f : 0.f);
-      if (lane == 0) obs_st(&row[p.o_buy + NMMO_MARKET_ROWS], 1.f);
-      nbytes += 4ull * (p.o_agent_id + 2 - NMMO_MARKET_ROWS + n);  // every mask but Buy's tail, id, tick
+        obs_st(&row[kWireBuyLo + k], mask_value<kWrap>(p, T, S, vis, inv, mpo, nm, m, 2, k) ? 1.f : 0.f);
+      if (lane == 0) obs_st(&row[kWireBuyLo + NMMO_MARKET_ROWS], 1.f);
+      nbytes += 4ull * (kFlatId + 2 - NMMO_MARKET_ROWS + n);  // every mask but Buy's tail, id, tick
     }
     mask_sec_f32<3, kWrap>(p, T, S, vis, inv, mpo, nm, m, row);
     mask_sec_f32<4, kWrap>(p, T, S, vis, inv, mpo, nm, m, row);
@@ -426,8 +377,8 @@ obs_kernel(ObsParams p) {
     mask_sec_f32<9, kWrap>(p, T, S, vis, inv, mpo, nm, m, row);
     mask_sec_f32<10, kWrap>(p, T, S, vis, inv, mpo, nm, m, row);
     mask_sec_f32<11, kWrap>(p, T, S, vis, inv, mpo, nm, m, row);
-    if (lane == 0) obs_st(&row[p.o_agent_id], (float)aid);
-    if (lane == 1) obs_st(&row[p.o_tick], (float)tick);
+    if (lane == 0) obs_st(&row[kFlatId], (float)aid);
+    if (lane == 1) obs_st(&row[kFlatTick], (float)tick);
     // Entity rows: two per pass (lanes 0-30 row k, lanes 32-62 row k + 1: 62 contiguous floats),
     // the rows past the visible ones as one zero run
     {
@@ -437,24 +388,24 @@ obs_kernel(ObsParams p) {
       for (int k0 = 0; k0 < nv2; k0 += 2) {
         const int k = k0 + half;
         if (f < NMMO_N_ENTITY_COLS)
-          obs_st(&row[p.o_entity + k * NMMO_N_ENTITY_COLS + f], k < m.nv ? (float)T[f * S + vis[k]] : 0.f);
+          obs_st(&row[kFlatEntity + k * NMMO_N_ENTITY_COLS + f], k < m.nv ? (float)T[f * S + vis[k]] : 0.f);
       }
       const int hz = max(nv2, hv);  // the rows past the visible ones not known zero
-      wave_zero(row, p.o_entity + nv2 * NMMO_N_ENTITY_COLS, p.o_entity + hz * NMMO_N_ENTITY_COLS);
-      nbytes += 4ull * (hz * NMMO_N_ENTITY_COLS + kInv * 16 + max(nm, hm) * 16 + 225 * 3);
+      wave_zero(row, kFlatEntity + nv2 * NMMO_N_ENTITY_COLS, kFlatEntity + hz * NMMO_N_ENTITY_COLS);
+      nbytes += 4ull * (hz * NMMO_N_ENTITY_COLS + kInv * kItemCols + max(nm, hm) * kItemCols + kTileN);
       if (p.ztag && lane == 0) {
         if (!zv) p.zrow[(size_t)e * p.P + a] = p.ztag;
         p.zst[(size_t)e * p.P + a] = zs_pack(nv2, nm, __builtin_amdgcn_readlane(my_task, j));
       }
     }
     // Inventory (own items, owner = self) and Market (env listings, ascending row)
-    for (int k = lane; k < kInv * 16; k += 64) {
+    for (int k = lane; k < kInv * kItemCols; k += 64) {
       const int q = k >> 4;
-      obs_st(&row[p.o_inventory + k], q < m.ninv ? item_col(inv[q], aid, k & 15) : 0.f);
+      obs_st(&row[kFlatInv + k], q < m.ninv ? item_col(inv[q], aid, k & 15) : 0.f);
     }
-    for (int k = lane; k < nm * 16; k += 64)
-      obs_st(&row[p.o_market + k], item_col(mitem[k >> 4], (mpo[k >> 4] >> 8) + 1, k & 15));
-    wave_zero(row, p.o_market + nm * 16, p.o_market + max(nm, hm) * 16);
+    for (int k = lane; k < nm * kItemCols; k += 64)
+      obs_st(&row[kFlatMarket + k], item_col(mitem[k >> 4], (mpo[k >> 4] >> 8) + 1, k & 15));
+    wave_zero(row, kFlatMarket + nm * kItemCols, kFlatMarket + max(nm, hm) * kItemCols);
     __builtin_amdgcn_wave_barrier();
   }
   if (p.rows_out && lane == 0 && nrows) {  // per env: one address per env keeps the atomics uncontended
@@ -512,21 +463,21 @@ __global__ void __launch_bounds__(256) expand_kernel(ObsParams p) {
     const int16_t* q = reinterpret_cast<const int16_t*>(nrow + NMMO_NATIVE_MASK_BYTES);
     const int frow = p.row_map ? p.row_map[(size_t)e * p.P + a] : e * p.P + a;
     if (frow < 0) continue;  // storage: row not kept (wave-uniform)
-    float* row = p.obs + (size_t)frow * p.elems;
+    float* row = p.obs + (size_t)frow * flat_elems(p.task_dim);
     const int aid = __builtin_amdgcn_readfirstlane(q[0]);
     if (aid == 0) {  // not in the realm: all-zero row
-      wave_zero(row, 0, p.elems);
+      wave_zero(row, 0, flat_elems(p.task_dim));
       continue;
     }
-    for (int j = lane; j < p.o_agent_id; j += 64) obs_st(&row[j], (float)nrow[j]);
-    if (lane == 0) obs_st(&row[p.o_agent_id], (float)aid);
-    if (lane == 1) obs_st(&row[p.o_tick], (float)q[1]);
-    for (int j = lane; j < kNObs * NMMO_N_ENTITY_COLS; j += 64) obs_st(&row[p.o_entity + j], (float)q[kNatEntity + j]);
-    for (int j = lane; j < kInv * 16; j += 64) obs_st(&row[p.o_inventory + j], (float)q[kNatInv + j]);
-    for (int j = lane; j < NMMO_MARKET_ROWS * 16; j += 64) obs_st(&row[p.o_market + j], (float)mk[j]);
+    for (int j = lane; j < kMaskN; j += 64) obs_st(&row[j], (float)nrow[j]);
+    if (lane == 0) obs_st(&row[kFlatId], (float)aid);
+    if (lane == 1) obs_st(&row[kFlatTick], (float)q[1]);
+    for (int j = lane; j < kNObs * NMMO_N_ENTITY_COLS; j += 64) obs_st(&row[kFlatEntity + j], (float)q[kNatEntity + j]);
+    for (int j = lane; j < kInv * kItemCols; j += 64) obs_st(&row[kFlatInv + j], (float)q[kNatInv + j]);
+    for (int j = lane; j < NMMO_MARKET_ROWS * kItemCols; j += 64) obs_st(&row[kFlatMarket + j], (float)mk[j]);
     const float* temb = p.task + (size_t)q[kNatTask] * p.task_dim;
-    for (int j = lane; j < p.task_dim; j += 64) obs_st(&row[p.o_task + j], temb[j]);
-    for (int j = lane; j < 225 * 3; j += 64) obs_st(&row[p.o_tile + j], (float)q[kNatTile + j]);
+    for (int j = lane; j < p.task_dim; j += 64) obs_st(&row[kFlatTask + j], temb[j]);
+    for (int j = lane; j < kTileN; j += 64) obs_st(&row[flat_tile(p.task_dim) + j], (float)q[kNatTile + j]);
     __builtin_amdgcn_wave_barrier();
   }
 }

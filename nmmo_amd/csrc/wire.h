@@ -29,19 +29,12 @@
 // distinct entities per agent) travels once.
 #pragma once
 
-#include "common.h"
+#include "obs_layout.h"
 
 namespace nmmo {
 
 constexpr int kWireHead = 16;
-constexpr int kWireBuyLo = 104, kWireBuyN = NMMO_MARKET_ROWS + 1;  // the Buy section's flat mask entries
-constexpr int kMaskN = 1586;                                       // ActionTargets entries (flat offset of AgentId)
-constexpr int kWireTiles = 114;                                    // 225 materials, two per byte (+ a zero byte)
-// flat offsets of the ActionTargets sections (nmmo_layout order)
-constexpr int kMkStyle = 0, kMkAttackT = 3, kMkDestroy = 1129, kMkGiveI = 1142, kMkGiveT = 1155, kMkGoldP = 1256,
-              kMkGoldT = 1355, kMkMove = 1456, kMkSellI = 1461, kMkSellP = 1474, kMkUse = 1573;
-constexpr int kNatI16Entity = 2, kNatI16Inv = kNatI16Entity + kNObs * NMMO_N_ENTITY_COLS,
-              kNatI16Tile = kNatI16Inv + kInv * 16, kNatI16Task = kNatI16Tile + 225 * 3;
+constexpr int kWireTiles = (kWinTiles + 1) / 2 + 1;  // 225 materials, two per byte (+ a zero byte): 114
 // the mask bit stream: 3 nv + 4 ninv bits in whole u16 words
 __host__ __device__ inline int wire_stream_bytes(int nv, int ninv) { return 2 * ((3 * nv + 4 * ninv + 15) >> 4); }
 // record offsets (bytes from the record start)
@@ -75,9 +68,6 @@ __host__ __device__ inline int wire_record_bytes(uint32_t cnt) {
 }
 // an env's entity table of ne rows
 __host__ __device__ inline int wire_table_bytes(int ne) { return (kEntRow * ne + 15) & ~15; }
-__host__ __device__ inline size_t wire_native_env_bytes(int P) {
-  return (size_t)P * NMMO_NATIVE_ROW_BYTES + NMMO_NATIVE_MARKET_BYTES;
-}
 
 // Ranks by entity id: the env's distinct ids as a 65,536-bit set (2,048 words in LDS) and the
 // exclusive popcount prefix of its words (wave-summed, 2,048 ints); the table index of an id in

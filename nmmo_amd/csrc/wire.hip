@@ -42,9 +42,9 @@ __global__ void __launch_bounds__(128) wire_size_kernel(const uint16_t* counts, 
     v.cnt[(size_t)e * P + a] = c;
     bytes = wire_record_bytes(c);
     if (c & 0x8000u) {
-      const int16_t* ent = reinterpret_cast<const int16_t*>(native + (size_t)e * wire_native_env_bytes(P) +
+      const int16_t* ent = reinterpret_cast<const int16_t*>(native + (size_t)e * native_env_bytes(P) +
                                                             (size_t)a * NMMO_NATIVE_ROW_BYTES + NMMO_NATIVE_MASK_BYTES) +
-                           kNatI16Entity;
+                           kNatEntity;
       for (int k = 0; k < (int)(c & 127); k++) idset_add(ids, ent[NMMO_N_ENTITY_COLS * k]);
     }
   }
@@ -225,10 +225,10 @@ __global__ void __launch_bounds__(256) wire_pack_kernel(const uint8_t* native, u
   const uint16_t* cnt = v.cnt + (size_t)e * P;
   const int ne = v.ecount[e];
   record_offsets_wave0(cnt, P, off, wire_table_bytes(ne));
-  const uint8_t* nenv = native + (size_t)e * wire_native_env_bytes(P);
+  const uint8_t* nenv = native + (size_t)e * native_env_bytes(P);
   auto ent16 = [&](int a) {
     return reinterpret_cast<const int16_t*>(nenv + (size_t)a * NMMO_NATIVE_ROW_BYTES + NMMO_NATIVE_MASK_BYTES) +
-           kNatI16Entity;
+           kNatEntity;
   };
   // the env's id set again (every block of the env: the table ranks)
   idset_clear(ids);
@@ -285,17 +285,17 @@ __global__ void __launch_bounds__(256) wire_pack_kernel(const uint8_t* native, u
     if (lane == 0) {
       const int gold = ent[((size_t)e * NMMO_NF + F_GOLD) * S + a];  // the state the obs was taken from
       const uint4 head = make_uint4((uint32_t)(uint16_t)i16[0] | (uint32_t)(uint16_t)i16[1] << 16,
-                                    (uint32_t)(uint16_t)i16[kNatI16Task] | (uint32_t)(uint16_t)i16[kNatI16Tile] << 16,
-                                    (uint32_t)(uint16_t)i16[kNatI16Tile + 1] | wire_m5(nv, ninv, exch, pp1) << 16,
+                                    (uint32_t)(uint16_t)i16[kNatTask] | (uint32_t)(uint16_t)i16[kNatTile] << 16,
+                                    (uint32_t)(uint16_t)i16[kNatTile + 1] | wire_m5(nv, ninv, exch, pp1) << 16,
                                     wire_m6(style, move, ng, pp1) | (uint32_t)(uint16_t)gold << 16);
       *reinterpret_cast<uint4*>(rec) = head;
     }
     uint16_t* d16 = reinterpret_cast<uint16_t*>(rec + kWireHead);
-    for (int k = lane; k < nv; k += 64) d16[k] = (uint16_t)idrank(ids, pre, i16[kNatI16Entity + NMMO_N_ENTITY_COLS * k]);
+    for (int k = lane; k < nv; k += 64) d16[k] = (uint16_t)idrank(ids, pre, i16[kNatEntity + NMMO_N_ENTITY_COLS * k]);
     int16_t* s16 = reinterpret_cast<int16_t*>(d16 + nv);
-    for (int k = lane; k < ninv * 16; k += 64) s16[k] = i16[kNatI16Inv + k];
+    for (int k = lane; k < ninv * 16; k += 64) s16[k] = i16[kNatInv + k];
     uint8_t* mat = reinterpret_cast<uint8_t*>(s16 + ninv * 16);
-    auto tile = [&](int t) { return t < 225 ? (int)i16[kNatI16Tile + 3 * t + 2] & 15 : 0; };
+    auto tile = [&](int t) { return t < 225 ? (int)i16[kNatTile + 3 * t + 2] & 15 : 0; };
     for (int u = lane; u < kWireTiles; u += 64) mat[u] = (uint8_t)(tile(2 * u) | tile(2 * u + 1) << 4);
     // the stream: bit i of AttackTarget / GiveTarget / GoldTarget (i < nv), then Destroy / GiveItem /
     // SellItem / Use (i < ninv); a lane per bit, a byte per 8 lanes, then the zero pad
@@ -358,7 +358,7 @@ __global__ void __launch_bounds__(256) wire_unpack_kernel(const uint8_t* wire, u
   const int ne = min((int)v.ecount[e], kMaxSlots);
   record_offsets_wave0(cnt, P, off, wire_table_bytes(ne));
   __syncthreads();
-  uint8_t* nenv = native + (size_t)e * wire_native_env_bytes(P);
+  uint8_t* nenv = native + (size_t)e * native_env_bytes(P);
   const uint8_t* penv = v.base + v.env_off[e];
   const int nm = v.mcount[e];
   for (int k = threadIdx.x; k < wire_table_bytes(ne) / 16; k += blockDim.x) tab4[k] = reinterpret_cast<const uint4*>(penv)[k];
@@ -411,19 +411,19 @@ __global__ void __launch_bounds__(256) wire_unpack_kernel(const uint8_t* wire, u
     }
     auto val = [&](int k) -> uint32_t {
       int x;
-      if (k < kNatI16Entity) {
+      if (k < kNatEntity) {
         x = h16[k];
-      } else if (k < kNatI16Inv) {
-        const int j = k - kNatI16Entity, row = j / NMMO_N_ENTITY_COLS;
+      } else if (k < kNatInv) {
+        const int j = k - kNatEntity, row = j / NMMO_N_ENTITY_COLS;
         x = row < nv ? tab[min((int)idx[row], kMaxSlots - 1) * NMMO_N_ENTITY_COLS + j - row * NMMO_N_ENTITY_COLS] : 0;
-      } else if (k < kNatI16Tile) {
-        const int j = k - kNatI16Inv;
+      } else if (k < kNatTile) {
+        const int j = k - kNatInv;
         x = j < ninv * 16 ? s16[j] : 0;
-      } else if (k < kNatI16Task) {
-        const int j = k - kNatI16Tile, t = j / 3, comp = j - 3 * t;
+      } else if (k < kNatTask) {
+        const int j = k - kNatTile, t = j / 3, comp = j - 3 * t;
         x = comp == 0 ? r0 + t / 15 : comp == 1 ? c0 + t % 15 : wire_tile(mat, t);
       } else {
-        x = k == kNatI16Task ? task : 0;
+        x = k == kNatTask ? task : 0;
       }
       return (uint32_t)(uint16_t)x;
     };
@@ -452,6 +452,50 @@ __global__ void __launch_bounds__(64 * kCheckEnvsPerBlock) wire_check_many_kerne
   if (e >= b.n[i]) return;
   const int bad = wire_check_env(b.wire[i], b.n[i], P, b.expect[i], e);
   if (bad) atomicOr(status, bad);
+}
+
+// One record as a flat row, by one wave: every section but Market, which `market` writes between
+// Inventory and Task (the callers hold the listings differently). lb: the wave's LDS copy of the
+// record (record_to_lds), tab: the env's entity table, mk / nm: its listings (the Buy.MarketItem
+// mask is rebuilt from them).
+template <typename M>
+__device__ __forceinline__ void record_flat_row(const ObsParams& p, const uint8_t* lb, int nv, int ninv,
+                                                const int16_t* tab, const int16_t* mk, int nm, float* row, M market) {
+  const int lane = lane_id();
+  const int16_t* h16 = reinterpret_cast<const int16_t*>(lb);
+  const uint16_t* idx = reinterpret_cast<const uint16_t*>(lb + kWireHead);
+  const int16_t* s16 = reinterpret_cast<const int16_t*>(lb + wire_off_inv(nv));  // Inventory rows
+  const uint8_t* mat = lb + wire_off_mat(nv, ninv);
+  const uint8_t* st = lb + wire_off_stream(nv, ninv);
+  const bool exch = wire_exch(h16);
+  const int gold = h16[7], aid = h16[0];
+  for (int j = lane; j < kMaskN; j += 64) {
+    bool m;
+    if (j >= kWireBuyLo && j < kWireBuyLo + kWireBuyN) {  // Buy.MarketItem from the listings
+      const int k = j - kWireBuyLo;
+      m = k == NMMO_MARKET_ROWS || (exch && k < nm && mk[kItemCols * k + 15] <= gold && mk[kItemCols * k + 2] != aid);
+    } else {
+      m = wire_mask_entry(j, h16, st, nv, ninv);
+    }
+    row[j] = m ? 1.f : 0.f;
+  }
+  if (lane == 0) row[kFlatId] = (float)h16[0];
+  if (lane == 1) row[kFlatTick] = (float)h16[1];
+  for (int j = lane; j < kNObs * NMMO_N_ENTITY_COLS; j += 64) {
+    const int k = j / NMMO_N_ENTITY_COLS;
+    row[kFlatEntity + j] =
+        k < nv ? (float)tab[min((int)idx[k], kMaxSlots - 1) * NMMO_N_ENTITY_COLS + j - k * NMMO_N_ENTITY_COLS] : 0.f;
+  }
+  for (int j = lane; j < kInv * kItemCols; j += 64) row[kFlatInv + j] = j < ninv * kItemCols ? (float)s16[j] : 0.f;
+  market();
+  const float* temb = p.task + (size_t)h16[2] * p.task_dim;
+  for (int j = lane; j < p.task_dim; j += 64) row[kFlatTask + j] = temb[j];
+  const int r0 = h16[3], c0 = h16[4];
+  float* tile = row + flat_tile(p.task_dim);
+  for (int j = lane; j < kTileN; j += 64) {
+    const int t = j / kTileCols, comp = j - kTileCols * t;
+    tile[j] = comp == 0 ? (float)(r0 + t / 15) : comp == 1 ? (float)(c0 + t % 15) : (float)wire_tile(mat, t);
+  }
 }
 
 // Wire records -> flat float32 rows (the pufferlib row of SPEC §8; bit-identical to
@@ -487,47 +531,19 @@ __global__ void __launch_bounds__(256) wire_expand_kernel(ObsParams p) {
     if (a >= P) break;
     const int frow = p.row_map ? p.row_map[(size_t)e * P + a] : e * P + a;
     if (frow < 0) continue;  // wave-uniform
-    float* row = p.obs + (size_t)frow * p.elems;
+    float* row = p.obs + (size_t)frow * flat_elems(p.task_dim);
     const uint32_t c = cnt[a];
     if (!(c & 0x8000u)) {  // not in the realm: all-zero row
-      wave_zero(row, 0, p.elems);
+      wave_zero(row, 0, flat_elems(p.task_dim));
       continue;
     }
     const int nv = c & 127, ninv = (c >> 7) & 15;
     record_to_lds(penv + off[a], wire_record_bytes(c) / 16, lrec);
-    const int16_t* h16 = reinterpret_cast<const int16_t*>(lb);
-    const uint16_t* idx = reinterpret_cast<const uint16_t*>(lb + kWireHead);
-    const int16_t* s16 = reinterpret_cast<const int16_t*>(lb + wire_off_inv(nv));  // Inventory rows
-    const uint8_t* mat = lb + wire_off_mat(nv, ninv);
-    const uint8_t* st = lb + wire_off_stream(nv, ninv);
-    const bool exch = wire_exch(h16);
-    const int gold = h16[7], aid = h16[0];
-    for (int j = lane; j < p.o_agent_id; j += 64) {
-      bool m;
-      if (j >= kWireBuyLo && j < kWireBuyLo + kWireBuyN) {  // Buy.MarketItem from the staged listings
-        const int k = j - kWireBuyLo;
-        m = k == NMMO_MARKET_ROWS || (exch && k < nm && mk[16 * k + 15] <= gold && mk[16 * k + 2] != aid);
-      } else {
-        m = wire_mask_entry(j, h16, st, nv, ninv);
-      }
-      row[j] = m ? 1.f : 0.f;
-    }
-    if (lane == 0) row[p.o_agent_id] = (float)h16[0];
-    if (lane == 1) row[p.o_tick] = (float)h16[1];
-    for (int j = lane; j < kNObs * NMMO_N_ENTITY_COLS; j += 64) {
-      const int k = j / NMMO_N_ENTITY_COLS;
-      row[p.o_entity + j] =
-          k < nv ? (float)tab[min((int)idx[k], kMaxSlots - 1) * NMMO_N_ENTITY_COLS + j - k * NMMO_N_ENTITY_COLS] : 0.f;
-    }
-    for (int j = lane; j < kInv * 16; j += 64) row[p.o_inventory + j] = j < ninv * 16 ? (float)s16[j] : 0.f;
-    for (int j = lane; j < NMMO_MARKET_ROWS * 16; j += 64) row[p.o_market + j] = (float)mk[j];
-    const float* temb = p.task + (size_t)h16[2] * p.task_dim;
-    for (int j = lane; j < p.task_dim; j += 64) row[p.o_task + j] = temb[j];
-    const int r0 = h16[3], c0 = h16[4];
-    for (int j = lane; j < 225 * 3; j += 64) {
-      const int t = j / 3, comp = j - 3 * t;
-      row[p.o_tile + j] = comp == 0 ? (float)(r0 + t / 15) : comp == 1 ? (float)(c0 + t % 15) : (float)wire_tile(mat, t);
-    }
+    record_flat_row(p, lb, nv, ninv, tab, mk, nm, row, [&]() {  // the staged, zero-padded Market block
+#pragma unroll 4  // eight copies per pass, as compiled before the row offset was a constant (the count comes
+               // out doubled; left alone the loop makes sixteen: 92 VGPRs instead of 68, occupancy 5 for 7)
+      for (int j = lane; j < NMMO_MARKET_ROWS * kItemCols; j += 64) row[kFlatMarket + j] = (float)mk[j];
+    });
     record_release();
   }
 }
@@ -535,8 +551,8 @@ __global__ void __launch_bounds__(256) wire_expand_kernel(ObsParams p) {
 // Flat rows of record-stored experience rows (nmmo_exp_gather_records): one wave per output row,
 // whose record may sit in any stored buffer and env, so nothing is staged per workgroup: the
 // wave finds the record (its env's count words -> offsets), copies it into its LDS slot and
-// writes the row with every value exactly as wire_expand_kernel computes it (entity-table rows,
-// listings and the Task embedding read through L2).
+// writes the row with wire_expand_kernel's record_flat_row (entity-table rows, listings and the
+// Task embedding read through L2).
 __global__ void __launch_bounds__(256) record_gather_kernel(ObsParams p, NmmoRecordStore rs, const int32_t* idx, int n,
                                                             float* out) {
   __shared__ uint4 recbuf[4][kRecMaxU4];
@@ -550,10 +566,10 @@ __global__ void __launch_bounds__(256) record_gather_kernel(ObsParams p, NmmoRec
   const uint16_t* cnt = v.cnt + (size_t)e * P;
   const int ne = min((int)v.ecount[e], kMaxSlots), nm = v.mcount[e];
   const uint8_t* penv = v.base + v.env_off[e];
-  float* row = out + (size_t)k * p.elems;
+  float* row = out + (size_t)k * flat_elems(p.task_dim);
   const uint32_t c = cnt[a];
   if (!(c & 0x8000u)) {  // not in the realm: all-zero row
-    wave_zero(row, 0, p.elems);
+    wave_zero(row, 0, flat_elems(p.task_dim));
     return;
   }
   // record offset (agents before a) and the listings' offset (all agents), after the table
@@ -573,46 +589,15 @@ __global__ void __launch_bounds__(256) record_gather_kernel(ObsParams p, NmmoRec
   const uint8_t* lb = reinterpret_cast<const uint8_t*>(lrec);
   const int nv = c & 127, ninv = (c >> 7) & 15;
   record_to_lds(penv + tb + before, wire_record_bytes(c) / 16, lrec);
-  const int16_t* h16 = reinterpret_cast<const int16_t*>(lb);
-  const uint16_t* ix = reinterpret_cast<const uint16_t*>(lb + kWireHead);
-  const int16_t* s16 = reinterpret_cast<const int16_t*>(lb + wire_off_inv(nv));  // Inventory rows
-  const uint8_t* mat = lb + wire_off_mat(nv, ninv);
-  const uint8_t* st = lb + wire_off_stream(nv, ninv);
-  const bool exch = wire_exch(h16);
-  const int gold = h16[7], aid = h16[0];
-  for (int j = lane; j < p.o_agent_id; j += 64) {
-    bool m;
-    if (j >= kWireBuyLo && j < kWireBuyLo + kWireBuyN) {  // Buy.MarketItem from the listings
-      const int q = j - kWireBuyLo;
-      m = q == NMMO_MARKET_ROWS || (exch && q < nm && mk[16 * q + 15] <= gold && mk[16 * q + 2] != aid);
-    } else {
-      m = wire_mask_entry(j, h16, st, nv, ninv);
-    }
-    row[j] = m ? 1.f : 0.f;
-  }
-  if (lane == 0) row[p.o_agent_id] = (float)h16[0];
-  if (lane == 1) row[p.o_tick] = (float)h16[1];
-  for (int j = lane; j < kNObs * NMMO_N_ENTITY_COLS; j += 64) {
-    const int q = j / NMMO_N_ENTITY_COLS;
-    row[p.o_entity + j] =
-        q < nv ? (float)tab[min((int)ix[q], kMaxSlots - 1) * NMMO_N_ENTITY_COLS + j - q * NMMO_N_ENTITY_COLS] : 0.f;
-  }
-  for (int j = lane; j < kInv * 16; j += 64) row[p.o_inventory + j] = j < ninv * 16 ? (float)s16[j] : 0.f;
-  for (int j = lane; j < nm * 16; j += 64) row[p.o_market + j] = (float)mk[j];
-  wave_zero(row, p.o_market + nm * 16, p.o_task);
-  const float* temb = p.task + (size_t)h16[2] * p.task_dim;
-  for (int j = lane; j < p.task_dim; j += 64) row[p.o_task + j] = temb[j];
-  const int r0 = h16[3], c0 = h16[4];
-  for (int j = lane; j < 225 * 3; j += 64) {
-    const int t = j / 3, comp = j - 3 * t;
-    row[p.o_tile + j] = comp == 0 ? (float)(r0 + t / 15) : comp == 1 ? (float)(c0 + t % 15) : (float)wire_tile(mat, t);
-  }
+  record_flat_row(p, lb, nv, ninv, tab, mk, nm, row, [&]() {  // the listings' rows, then a zero run
+    for (int j = lane; j < nm * kItemCols; j += 64) row[kFlatMarket + j] = (float)mk[j];
+    wave_zero(row, kFlatMarket + nm * kItemCols, kFlatTask);
+  });
 }
 
 hipError_t launch_record_gather(const ObsParams& p, const NmmoRecordStore& rs, const int32_t* idx, int n, float* out,
                                 hipStream_t s) {
   if (n <= 0) return hipSuccess;
-  if (p.o_task != p.o_market + NMMO_MARKET_ROWS * 16) return hipErrorInvalidValue;
   hipLaunchKernelGGL(record_gather_kernel, dim3((n + 3) / 4), dim3(256), 0, s, p, rs, idx, n, out);
   return hipGetLastError();
 }

@@ -74,14 +74,17 @@ def test_flat_layout_size_and_keys():
     assert top == sorted(top)  # pufferlib sorted-key flattening
 
 
-def test_three_layouts_agree(oracle_lib):
+@pytest.mark.parametrize("task_dim", [64, 2048, 2112])
+def test_three_layouts_agree(oracle_lib, task_dim):
+    """The Task width is the layout's one run-time value: it moves the Tile offset and the row length."""
     from nmmo_amd import _native
 
-    py = layout.flat_layout(2048)
-    lay = _native.layout(Config().to_c())
-    assert lay.obs_elems == py["__total__"].offset == oracle_lib.oracle_obs_elems(2048)
+    py = layout.flat_layout(task_dim)
+    lay = _native.layout(Config(TASK_EMBED_DIM=task_dim).to_c())
+    assert lay.obs_elems == py["__total__"].offset == oracle_lib.oracle_obs_elems(task_dim)
+    assert lay.off_tile == lay.off_task + task_dim and lay.obs_elems == lay.off_tile + 225 * 3
     offs = (ctypes.c_int32 * 20)()
-    oracle_lib.oracle_flat_offsets(2048, offs)
+    oracle_lib.oracle_flat_offsets(task_dim, offs)
     names = [f"ActionTargets.{a}.{b}" for a, b in REF_HEAD_KEYS] + [
         "AgentId", "CurrentTick", "Entity", "Inventory", "Market", "Task", "Tile"]
     c_offs = [lay.off_mask_attack_style, lay.off_mask_attack_target, lay.off_mask_buy,
