@@ -1,4 +1,4 @@
-"""Build libnmmo_hip.so and libnmmo_heads.so in-tree with hipcc for gfx950 (no JIT cache: the
+"""Build libnmmo_hip.so, libnmmo_heads.so and libnmmo_ppo.so in-tree with hipcc for gfx950 (no JIT cache: the
 libraries ship with the repo snapshot to the GPU box)."""
 
 from __future__ import annotations
@@ -22,6 +22,9 @@ ARCH = os.environ.get("NMMO_OFFLOAD_ARCH", "gfx950")
 HEADS_LIB_PATH = os.path.join(LIB_DIR, "libnmmo_heads.so")
 HEADS_SOURCES = ["heads.hip"]
 HEADS_HEADERS = ["common.h"]
+# the fused PPO minibatch loss (include/nmmo_ppo.h): a third library, for the same reason
+PPO_LIB_PATH = os.path.join(LIB_DIR, "libnmmo_ppo.so")
+PPO_SOURCES = ["ppo.hip"]
 
 
 def _hipcc() -> str:
@@ -59,6 +62,23 @@ def heads_stale() -> bool:
         return True
     with open(HEADS_LIB_PATH, "rb") as fh:
         return ("src=" + heads_source_hash()).encode() not in fh.read()
+
+
+def ppo_source_hash() -> str:
+    """source_hash() of libnmmo_ppo.so: ppo.hip (it includes no project header) and its C interface."""
+    h = hashlib.sha256()
+    for f in [os.path.join(CSRC, f) for f in PPO_SOURCES] + [os.path.join(HERE, "..", "include", "nmmo_ppo.h")]:
+        with open(f, "rb") as fh:
+            h.update(os.path.basename(f).encode() + b"\0" + fh.read())
+    return h.hexdigest()[:16]
+
+
+def ppo_stale() -> bool:
+    """True unless libnmmo_ppo.so exists and embeds the current ppo source hash."""
+    if not os.path.exists(PPO_LIB_PATH):
+        return True
+    with open(PPO_LIB_PATH, "rb") as fh:
+        return ("src=" + ppo_source_hash()).encode() not in fh.read()
 
 
 def stale() -> bool:
@@ -118,6 +138,23 @@ def build_heads(force: bool = False, verbose: bool = False) -> str:
     return HEADS_LIB_PATH
 
 
+def build_ppo(force: bool = False, verbose: bool = False) -> str:
+    """libnmmo_ppo.so (nmmo_amd/ppo.py), with the product library's flags."""
+    if not force and not ppo_stale():
+        return PPO_LIB_PATH
+    os.makedirs(LIB_DIR, exist_ok=True)
+    tmp = PPO_LIB_PATH + ".tmp"
+    cmd = [_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Werror",
+           "-ffp-contract=off", f'-DNMP_SRC_HASH="{ppo_source_hash()}"', "-shared",
+           *[os.path.join(CSRC, f) for f in PPO_SOURCES], "-o", tmp]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+    os.replace(tmp, PPO_LIB_PATH)
+    return PPO_LIB_PATH
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     print(build_heads(force="--force" in sys.argv, verbose=True))
+    print(build_ppo(force="--force" in sys.argv, verbose=True))

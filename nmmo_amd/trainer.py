@@ -52,6 +52,9 @@ class TrainConfig:
     batch_rows: int = 128
     bptt_horizon: int = 8
     vf_clip_coef: float = 0.1
+    # the minibatch loss as one `ppo.ppo_loss` call (the HIP kernel of SPEC.md §16) instead of the
+    # chain of torch ops; not part of the reference's config
+    fused_loss: bool = False
 
     def validate(self):
         if self.batch_size % (self.bptt_horizon * self.batch_rows):
@@ -179,6 +182,10 @@ class DeviceTrainer:
         b_returns, b_values, b_adv = b["b_returns"], b["b_values"], b["b_advantages"]
         pg_losses, entropy_losses, v_losses, clipfracs, old_kls, kls = [], [], [], [], [], []
         approx_kl = None
+        if cfg.fused_loss:
+            from . import ppo
+
+            acc = ppo.new_accumulator(self.device)  # the minibatch stats are summed on the device
         for _ in range(cfg.update_epochs):
             for mb in range(b["num_minibatches"]):
                 m = exp.minibatch(b["b_idxs"], mb)
@@ -188,6 +195,17 @@ class DeviceTrainer:
                 mb_advantages = b_adv[mb].reshape(-1)
                 mb_returns = b_returns[mb].reshape(-1)
                 _, newlogprob, entropy, newvalue = agent(mb_obs, action=mb_actions)
+                if cfg.fused_loss:
+                    loss, st = ppo.ppo_loss(
+                        newlogprob, entropy, newvalue.view(-1), m["logprobs"].reshape(-1), mb_advantages, mb_returns,
+                        mb_values, clip_coef=cfg.clip_coef, vf_clip_coef=cfg.vf_clip_coef, ent_coef=cfg.ent_coef,
+                        vf_coef=cfg.vf_coef, norm_adv=cfg.norm_adv, clip_vloss=cfg.clip_vloss, accum=acc)
+                    approx_kl = st[ppo.APPROX_KL]
+                    self.optimizer.zero_grad()
+                    loss.backward()
+                    nn.utils.clip_grad_norm_(agent.parameters(), cfg.max_grad_norm)
+                    self.optimizer.step()
+                    continue
                 logratio = newlogprob - m["logprobs"].reshape(-1)
                 ratio = logratio.exp()
                 with torch.no_grad():
@@ -226,6 +244,12 @@ class DeviceTrainer:
         losses = {"policy_loss": mean(pg_losses), "value_loss": mean(v_losses), "entropy": mean(entropy_losses),
                   "old_approx_kl": mean(old_kls), "approx_kl": mean(kls), "clipfrac": mean(clipfracs),
                   "explained_variance": explained_var}
+        if cfg.fused_loss:  # one host read for all of them
+            sums = acc.tolist()
+            for key, k in (("policy_loss", ppo.PG_LOSS), ("value_loss", ppo.V_LOSS), ("entropy", ppo.ENTROPY),
+                           ("old_approx_kl", ppo.OLD_APPROX_KL), ("approx_kl", ppo.APPROX_KL),
+                           ("clipfrac", ppo.CLIPFRAC)):
+                losses[key] = sums[k] / sums[ppo.N_STATS] if sums[ppo.N_STATS] else math.nan
         torch.cuda.synchronize(self.device)
         self.update += 1
         losses["train_time"] = time.perf_counter() - t0

@@ -2,8 +2,9 @@
 reference trainer's agent_SPS (clean_pufferl.py:364-376) with the HIP stepper, HBM storage and the
 small stand-in policy, plus the train side (sort, GAE, PPO epochs) per update.
 
-Usage (GPU box): python tools/bench_trainer.py [envs] [batch_size] [updates] [--fused-heads]
-(--fused-heads: the agent's action heads run as the fused HIP kernels, nmmo_amd/heads.py)
+Usage (GPU box): python tools/bench_trainer.py [envs] [batch_size] [updates] [--fused-heads] [--fused-loss]
+(--fused-heads: the agent's action heads run as the fused HIP kernels, nmmo_amd/heads.py;
+ --fused-loss: the PPO minibatch loss runs as the fused HIP kernel, nmmo_amd/ppo.py)
 """
 
 import json
@@ -22,7 +23,8 @@ from nmmo_amd.trainer import DeviceTrainer, MaskedLinearAgent, TrainConfig  # no
 
 def main():
     fused = "--fused-heads" in sys.argv
-    argv = [a for a in sys.argv if a != "--fused-heads"]
+    fused_loss = "--fused-loss" in sys.argv
+    argv = [a for a in sys.argv if a not in ("--fused-heads", "--fused-loss")]
     envs = int(argv[1]) if len(argv) > 1 else 64
     batch = int(argv[2]) if len(argv) > 2 else 32768
     updates = int(argv[3]) if len(argv) > 3 else 3
@@ -31,7 +33,7 @@ def main():
     eng = NmmoEngine(cfg, envs, seed=1)
     eng.reset()
     agent = MaskedLinearAgent(cfg.TASK_EMBED_DIM, fused_heads=fused, seed=1).cuda()
-    tc = TrainConfig(batch_size=batch, total_timesteps=batch * (updates + 1))
+    tc = TrainConfig(batch_size=batch, total_timesteps=batch * (updates + 1), fused_loss=fused_loss)
     tr = DeviceTrainer(eng, agent, tc)
     tr.evaluate()  # warm-up (allocator, kernels)
     tr.train()
@@ -41,8 +43,9 @@ def main():
         trn.append(tr.train())
     out = {
         "workload": f"C4 {envs} envs x 128 agents, flat obs, batch_size {batch}, MaskedLinearAgent"
-                    + (", fused heads" if fused else ""),
+                    + (", fused heads" if fused else "") + (", fused loss" if fused_loss else ""),
         "fused_heads": fused,
+        "fused_loss": fused_loss,
         "agent_SPS": round(sum(e["agent_SPS"] for e in ev) / len(ev)),
         "SPS": round(sum(e["SPS"] for e in ev) / len(ev)),
         "eval_time_s": round(sum(e["eval_time"] for e in ev) / len(ev), 4),
