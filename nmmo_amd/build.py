@@ -1,4 +1,4 @@
-"""Build libnmmo_hip.so, libnmmo_heads.so and libnmmo_ppo.so in-tree with hipcc for gfx950 (no JIT cache: the
+"""Build libnmmo_hip.so, libnmmo_heads.so, libnmmo_ppo.so and libnmmo_lstm.so in-tree with hipcc for gfx950 (no JIT cache: the
 libraries ship with the repo snapshot to the GPU box)."""
 
 from __future__ import annotations
@@ -25,6 +25,9 @@ HEADS_HEADERS = ["common.h"]
 # the fused PPO minibatch loss (include/nmmo_ppo.h): a third library, for the same reason
 PPO_LIB_PATH = os.path.join(LIB_DIR, "libnmmo_ppo.so")
 PPO_SOURCES = ["ppo.hip"]
+# the fused LSTM recurrence (include/nmmo_lstm.h): a fourth library, for the same reason
+LSTM_LIB_PATH = os.path.join(LIB_DIR, "libnmmo_lstm.so")
+LSTM_SOURCES = ["lstm.hip"]
 
 
 def _hipcc() -> str:
@@ -79,6 +82,23 @@ def ppo_stale() -> bool:
         return True
     with open(PPO_LIB_PATH, "rb") as fh:
         return ("src=" + ppo_source_hash()).encode() not in fh.read()
+
+
+def lstm_source_hash() -> str:
+    """source_hash() of libnmmo_lstm.so: lstm.hip (it includes no project header) and its C interface."""
+    h = hashlib.sha256()
+    for f in [os.path.join(CSRC, f) for f in LSTM_SOURCES] + [os.path.join(HERE, "..", "include", "nmmo_lstm.h")]:
+        with open(f, "rb") as fh:
+            h.update(os.path.basename(f).encode() + b"\0" + fh.read())
+    return h.hexdigest()[:16]
+
+
+def lstm_stale() -> bool:
+    """True unless libnmmo_lstm.so exists and embeds the current lstm source hash."""
+    if not os.path.exists(LSTM_LIB_PATH):
+        return True
+    with open(LSTM_LIB_PATH, "rb") as fh:
+        return ("src=" + lstm_source_hash()).encode() not in fh.read()
 
 
 def stale() -> bool:
@@ -154,7 +174,24 @@ def build_ppo(force: bool = False, verbose: bool = False) -> str:
     return PPO_LIB_PATH
 
 
+def build_lstm(force: bool = False, verbose: bool = False) -> str:
+    """libnmmo_lstm.so (nmmo_amd/lstm.py), with the product library's flags."""
+    if not force and not lstm_stale():
+        return LSTM_LIB_PATH
+    os.makedirs(LIB_DIR, exist_ok=True)
+    tmp = LSTM_LIB_PATH + ".tmp"
+    cmd = [_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Werror",
+           "-ffp-contract=off", f'-DNML_SRC_HASH="{lstm_source_hash()}"', "-shared",
+           *[os.path.join(CSRC, f) for f in LSTM_SOURCES], "-o", tmp]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+    os.replace(tmp, LSTM_LIB_PATH)
+    return LSTM_LIB_PATH
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     print(build_heads(force="--force" in sys.argv, verbose=True))
     print(build_ppo(force="--force" in sys.argv, verbose=True))
+    print(build_lstm(force="--force" in sys.argv, verbose=True))

@@ -14,6 +14,11 @@ The policy networks themselves are out of scope (consumers of the
 `MaskedLinearAgent` is a minimal stand-in with the reference policies' call convention —
 `agent(obs, action=None) -> (action, logprob, entropy, value)` with every head's logits masked
 by the obs ActionTargets (baseline_policy.py:245-262) — so the loop can be exercised and timed.
+`RecurrentMaskedAgent` is the same stand-in with an LSTM between encoder and heads and the
+reference's recurrent convention, `agent(obs, state, action=None) -> (..., state)`: for an agent
+with an `.lstm` attribute the loop carries one LSTM state per agent slot through `evaluate()` and
+trains over `[batch_rows, bptt_horizon]` windows, the state handed from one minibatch to the next
+(clean_pufferl.py:177-182, :310-324, :454-469; SPEC.md §17).
 """
 
 from __future__ import annotations
@@ -88,7 +93,10 @@ class MaskedLinearAgent(nn.Module):
     def forward(self, obs: torch.Tensor, action: torch.Tensor | None = None):
         mat = obs[:, self.o_tile + 2:self.o_tile + 3 * layout.TILE_ROWS:3] / 16.0
         tick = obs[:, self.o_tick:self.o_tick + 1] / 1024.0
-        h = self.encoder(torch.cat([mat, tick], 1))
+        return self.heads(self.encoder(torch.cat([mat, tick], 1)), obs, action)
+
+    def heads(self, h: torch.Tensor, obs: torch.Tensor, action: torch.Tensor | None = None):
+        """The masked action heads and the value head on the hidden rows `h` of the rows `obs`."""
         logits = self.actor(h)
         if self.fused_heads:
             from .heads import masked_heads
@@ -110,6 +118,48 @@ class MaskedLinearAgent(nn.Module):
         return torch.stack(acts, 1), logp, ent, self.value(h)
 
 
+class RecurrentMaskedAgent(MaskedLinearAgent):
+    """The stand-in with an LSTM between its encoder and its heads, in the calling convention of
+    the reference's recurrent policies (pufferlib's Recurrent wrapper; clean_pufferl.py:317-324,
+    :465-469): `agent(obs, state=None, action=None) -> (action, logprob, entropy, value, state)`.
+
+    obs is [B, E] (one step) or [B, T, E] (a window); the four outputs are flattened in (B, T)
+    order; state is (h, c), each [num_layers, B, hidden]. `fused_lstm=True` runs the recurrence
+    as `lstm.LSTM` (the HIP kernels of SPEC.md §17) instead of `torch.nn.LSTM`: under
+    `torch.no_grad()` a given state is then updated in place and returned."""
+
+    def __init__(self, task_dim: int = 2048, hidden: int = 64, fused_heads: bool = False, seed: int = 0,
+                 fused_lstm: bool = False, num_layers: int = 1):
+        super().__init__(task_dim, hidden, fused_heads, seed)
+        self.fused_lstm = bool(fused_lstm)
+        if self.fused_lstm:
+            from .lstm import LSTM
+
+            self.lstm = LSTM(hidden, hidden, num_layers)
+        else:
+            self.lstm = nn.LSTM(hidden, hidden, num_layers)
+
+    def hidden(self, obs: torch.Tensor, state=None):
+        """Encoder and LSTM: (hidden rows [B * T, hidden] in (B, T) order, the obs rows in that
+        order, the new state)."""
+        B, T = obs.shape[0], (obs.shape[1] if obs.dim() == 3 else 1)
+        flat = obs.reshape(B * T, obs.shape[-1])
+        mat = flat[:, self.o_tile + 2:self.o_tile + 3 * layout.TILE_ROWS:3] / 16.0
+        tick = flat[:, self.o_tick:self.o_tick + 1] / 1024.0
+        x = self.encoder(torch.cat([mat, tick], 1)).view(B, T, -1).transpose(0, 1)  # time first
+        if self.fused_lstm and state is not None and not torch.is_grad_enabled():
+            y, state = self.lstm(x, state, out=state)
+        else:
+            y, state = self.lstm(x, state)
+        return y.transpose(0, 1).reshape(B * T, -1), flat, state
+
+    def forward(self, obs: torch.Tensor, state=None, action: torch.Tensor | None = None):
+        h, flat, state = self.hidden(obs, state)
+        if action is not None:
+            action = action.reshape(h.shape[0], -1)
+        return (*self.heads(h, flat, action), state)
+
+
 class DeviceTrainer:
     """clean_pufferl's evaluate()/train() over one NmmoEngine (flat obs) and DeviceExperience."""
 
@@ -129,6 +179,12 @@ class DeviceTrainer:
         self.agent_step = 0
         self.last_batch = None
         self.stats = {}
+        # one LSTM state per agent slot (clean_pufferl.py:177-182), carried across evaluate() calls
+        # and, as in the reference, not reset when an agent dies or an env resets
+        self.next_lstm_state = None
+        if hasattr(agent, "lstm"):
+            shape = (agent.lstm.num_layers, self.n_rows, agent.lstm.hidden_size)
+            self.next_lstm_state = (torch.zeros(shape, device=self.device), torch.zeros(shape, device=self.device))
 
     def evaluate(self, on_store=None) -> dict:
         """One batch of experience (clean_pufferl.py:287-357): recv -> forward -> store -> send
@@ -147,7 +203,11 @@ class DeviceTrainer:
             o = eng.obs.view(N, eng.obs_elems)
             r, d, mask = eng.rew.view(N), eng.term.view(N), eng.mask.view(N)
             with torch.no_grad():
-                actions, logprob, _, value = self.agent(o)
+                if self.next_lstm_state is not None:
+                    # rows are in identity order: no gather or scatter by env_id (:310-324)
+                    actions, logprob, _, value, self.next_lstm_state = self.agent(o, self.next_lstm_state)
+                else:
+                    actions, logprob, _, value = self.agent(o)
             agent_steps += mask.sum()
             padded += N
             exp.store(o, r, d, mask, actions, logprob, value.flatten(), step, env_id_base=self.env_id_base)
@@ -186,15 +246,23 @@ class DeviceTrainer:
             from . import ppo
 
             acc = ppo.new_accumulator(self.device)  # the minibatch stats are summed on the device
+        recurrent = hasattr(agent, "lstm")
         for _ in range(cfg.update_epochs):
+            lstm_state = None  # clean_pufferl.py:455
             for mb in range(b["num_minibatches"]):
                 m = exp.minibatch(b["b_idxs"], mb)
-                mb_obs = m["obs"].reshape(-1, exp.obs_elems)
                 mb_actions = m["actions"].reshape(-1, m["actions"].shape[-1])
                 mb_values = b_values[mb].reshape(-1)
                 mb_advantages = b_adv[mb].reshape(-1)
                 mb_returns = b_returns[mb].reshape(-1)
-                _, newlogprob, entropy, newvalue = agent(mb_obs, action=mb_actions)
+                if recurrent:
+                    # [batch_rows, bptt_horizon, obs_elems]; the state goes on to the next minibatch (:465-469)
+                    mb_obs = m["obs"].reshape(cfg.batch_rows, cfg.bptt_horizon, exp.obs_elems)
+                    _, newlogprob, entropy, newvalue, lstm_state = agent(mb_obs, state=lstm_state, action=mb_actions)
+                    lstm_state = (lstm_state[0].detach(), lstm_state[1].detach())
+                else:
+                    mb_obs = m["obs"].reshape(-1, exp.obs_elems)
+                    _, newlogprob, entropy, newvalue = agent(mb_obs, action=mb_actions)
                 if cfg.fused_loss:
                     loss, st = ppo.ppo_loss(
                         newlogprob, entropy, newvalue.view(-1), m["logprobs"].reshape(-1), mb_advantages, mb_returns,

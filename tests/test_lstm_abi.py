@@ -1,0 +1,197 @@
+"""libnmmo_lstm.so (include/nmmo_lstm.h) loads without a GPU, exports exactly the nml_* symbols its
+header declares, and reports argument errors through the return code + nml_last_error without
+touching a GPU; the three other libraries export no nml_ symbol. `lstm.LSTM` carries
+torch.nn.LSTM's parameter names and shapes. CPU only."""
+
+import os
+import re
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "nmmo_lstm.h")
+P = 0x1000  # a non-null dummy pointer: never dereferenced
+FUNCS = {"nml_cell", "nml_seq_forward", "nml_seq_backward", "nml_last_error", "nml_build_info"}
+
+
+@pytest.fixture(scope="module")
+def lstm():
+    from nmmo_amd import lstm
+
+    lstm.lib()
+    return lstm
+
+
+def exports(name):
+    out = subprocess.check_output(["nm", "-D", "--defined-only", os.path.join(ROOT, "nmmo_amd", "lib", name)]).decode()
+    return set(re.findall(r"\sT\s(\w+)", out))
+
+
+def test_library_loads_and_embeds_its_source_hash(lstm):
+    from nmmo_amd import build
+
+    assert not build.lstm_stale()
+    info = lstm.lib().nml_build_info().decode()
+    assert "src=" + build.lstm_source_hash() in info and "arch=gfx950" in info and "fp_contract=off" in info
+
+
+def test_exports_equal_header_declarations(lstm):
+    decl = re.findall(r"NML_API\s+[\w\s\*]+?\b(nml_\w+)\s*\(", open(HEADER).read())
+    assert set(decl) == FUNCS and len(decl) == len(FUNCS)
+    assert set(decl) == {s for s in exports("libnmmo_lstm.so") if s.startswith("nm")}
+    assert set(decl) == set(lstm.SYMBOLS)
+    for name in decl:
+        getattr(lstm.lib(), name)
+
+
+def test_other_libraries_export_no_nml_symbol():
+    from nmmo_amd import _native, heads, ppo
+
+    hip, hd, pp = exports("libnmmo_hip.so"), exports("libnmmo_heads.so"), exports("libnmmo_ppo.so")
+    assert not {s for s in hip | hd | pp if s.startswith("nml_")}
+    assert {s for s in hip if s.startswith("nmmo_")} == set(_native.SYMBOLS)
+    assert {s for s in hd if s.startswith("nm")} == set(heads.SYMBOLS)
+    assert {s for s in pp if s.startswith("nm")} == set(ppo.SYMBOLS)
+    for header in ("nmmo_hip.h", "nmmo_heads.h", "nmmo_ppo.h"):
+        assert "nml_" not in open(os.path.join(ROOT, "include", header)).read()
+
+
+def test_constants_match_header(lstm):
+    text = open(HEADER).read()
+    for macro, val in [("NML_OK", lstm.NML_OK), ("NML_E_INVALID", lstm.NML_E_INVALID), ("NML_E_HIP", lstm.NML_E_HIP),
+                       ("NML_H_STEP", lstm.H_STEP), ("NML_MAX_H", lstm.MAX_H), ("NML_MAX_B", lstm.MAX_B),
+                       ("NML_MAX_T", lstm.MAX_T), ("NML_ROWS", lstm.ROWS)]:
+        m = re.search(rf"#define {macro} (.*?)(?:/\*|$)", text, re.M)
+        assert eval(m.group(1).strip()) == val, macro
+    assert lstm.H_STEP == 64 and lstm.MAX_H == 1024
+
+
+# (function, number of leading int arguments, pointer arguments that may be NULL, pointer count)
+CALLS = {
+    "nml_cell": (("B", "H"), {1, 2, 3, 7}, 8),  # gb, b_ih, b_hh, gates_out
+    "nml_seq_forward": (("T", "B", "H"), {2, 3}, 11),  # b_ih, b_hh
+    "nml_seq_backward": (("T", "B", "H"), set(), 10),
+}
+
+
+def call(lstm, fn, ptrs=None, **dims):
+    ints, _, n = CALLS[fn]
+    shape = dict(T=8, B=128, H=256)
+    shape.update(dims)
+    ptrs = [P] * n if ptrs is None else ptrs
+    return getattr(lstm.lib(), fn)(*[shape[k] for k in ints], *ptrs, None)
+
+
+@pytest.mark.parametrize("fn", sorted(CALLS))
+def test_argument_errors_are_reported_without_a_gpu(lstm, fn):
+    """Every pointer is a non-null dummy that is never dereferenced: each call must fail its
+    argument check before any launch."""
+    L, E = lstm.lib(), lstm.NML_E_INVALID
+    ints, optional, n = CALLS[fn]
+
+    def bad(what, ptrs=None, **dims):
+        assert call(lstm, fn, ptrs, **dims) == E, what
+        msg = L.nml_last_error()
+        assert fn.encode() in msg and what.encode() in msg, (what, msg)
+
+    bad("B -1", B=-1)
+    bad(f"B {lstm.MAX_B + 1}", B=lstm.MAX_B + 1)
+    for h in (0, 96, -64, 32, lstm.MAX_H + 64, 2048):
+        bad(f"H {h}", H=h)
+    if "T" in ints:
+        bad("T 0", T=0)
+        bad("T -1", T=-1)
+        bad(f"T {lstm.MAX_T + 1}", T=lstm.MAX_T + 1)
+    for i in range(n):
+        ptrs = [P] * n
+        ptrs[i] = None
+        if i in optional:
+            assert call(lstm, fn, ptrs, B=0) == lstm.NML_OK, i
+        else:
+            bad("is NULL", ptrs)
+            assert call(lstm, fn, ptrs, B=0) == E, i  # an error even with no rows
+    # no rows is a successful no-op that launches nothing, at every supported H
+    for h in (64, 320, lstm.MAX_H):
+        assert call(lstm, fn, B=0, H=h) == lstm.NML_OK
+    # the extreme legal sizes pass the range checks (and fail on the NULL pointer)
+    assert call(lstm, fn, [None] + [P] * (n - 1), T=lstm.MAX_T, B=lstm.MAX_B, H=lstm.MAX_H) == E
+    assert b"NULL" in L.nml_last_error()
+
+
+def test_python_wrapper_refuses_host_tensors(lstm):
+    import torch
+
+    rnn = lstm.LSTM(24, 64)
+    with pytest.raises(lstm.LstmError):  # no torch fallback: host tensors are an error
+        rnn(torch.zeros(2, 3, 24))
+    with torch.no_grad(), pytest.raises(lstm.LstmError):
+        rnn(torch.zeros(2, 3, 24))
+    z = torch.zeros(3, 64)
+    with pytest.raises(lstm.LstmError):
+        lstm.cell(torch.zeros(3, 256), None, None, None, z, z.clone(), z)
+
+
+def test_module_refuses_unsupported_hidden_sizes(lstm):
+    for h in (0, 32, 96, lstm.MAX_H + 64):
+        with pytest.raises(ValueError, match=str(h)):
+            lstm.LSTM(24, h)
+
+
+def test_state_dict_moves_both_ways_with_torch_lstm(lstm):
+    import torch
+
+    torch.manual_seed(3)
+    ours, theirs = lstm.LSTM(24, 64, 2), torch.nn.LSTM(24, 64, 2)
+    assert ours.num_layers == theirs.num_layers == 2 and ours.hidden_size == theirs.hidden_size == 64
+    sd, td = ours.state_dict(), theirs.state_dict()
+    assert list(sd) == list(td)
+    assert {k: tuple(v.shape) for k, v in sd.items()} == {k: tuple(v.shape) for k, v in td.items()}
+    assert any(not torch.equal(sd[k], td[k]) for k in sd)
+    bound = 1 / 8  # torch.nn.LSTM's initialisation: U(-1/sqrt(H), 1/sqrt(H))
+    assert all(float(v.abs().max()) <= bound and float(v.abs().max()) > bound / 2 for v in sd.values())
+    ours.load_state_dict(td)
+    assert all(torch.equal(v, td[k]) for k, v in ours.state_dict().items())
+    fresh = lstm.LSTM(24, 64, 2)
+    theirs.load_state_dict(fresh.state_dict())
+    assert all(torch.equal(v, theirs.state_dict()[k]) for k, v in fresh.state_dict().items())
+
+
+def test_recurrent_agent_defaults_to_torch_lstm():
+    import torch
+
+    from nmmo_amd.trainer import MaskedLinearAgent, RecurrentMaskedAgent
+
+    agent = RecurrentMaskedAgent()
+    assert agent.fused_lstm is False and agent.fused_heads is False
+    assert isinstance(agent.lstm, torch.nn.LSTM) and agent.lstm.hidden_size == 64 and agent.lstm.num_layers == 1
+    assert not hasattr(MaskedLinearAgent(), "lstm")
+    from nmmo_amd import lstm
+
+    fused = RecurrentMaskedAgent(fused_lstm=True)
+    assert isinstance(fused.lstm, lstm.LSTM) and list(fused.state_dict()) == list(agent.state_dict())
+
+
+def test_recurrent_agent_window_equals_its_steps_on_the_cpu():
+    """The calling convention with torch.nn.LSTM on the host: a [B, T, E] window gives, in (B, T)
+    order, what T single-step calls that hand the state on give."""
+    import torch
+
+    from nmmo_amd import layout
+    from nmmo_amd.trainer import RecurrentMaskedAgent
+
+    torch.manual_seed(5)
+    B, T, E = 3, 4, layout.flat_layout(2048)["Tile"].offset + 3 * layout.TILE_ROWS + 64
+    agent = RecurrentMaskedAgent(num_layers=2).double()
+    obs = torch.randint(0, 3, (B, T, E)).double()
+    with torch.no_grad():
+        acts, _, _, _, _ = agent(obs)
+        _, logp, ent, value, state = agent(obs, action=acts)
+        assert acts.shape == (B * T, len(agent.dims)) and logp.shape == ent.shape == (B * T,) and value.shape == (B * T, 1)
+        assert state[0].shape == state[1].shape == (2, B, 64)
+        st = None
+        for t in range(T):
+            _, lp, en, v, st = agent(obs[:, t], st, action=acts.view(B, T, -1)[:, t])
+            assert torch.allclose(lp, logp.view(B, T)[:, t], rtol=0, atol=1e-12)
+            assert torch.allclose(v, value.view(B, T, 1)[:, t], rtol=0, atol=1e-12)
+        assert torch.allclose(st[0], state[0], rtol=0, atol=1e-12) and torch.allclose(st[1], state[1], rtol=0, atol=1e-12)

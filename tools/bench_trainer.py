@@ -3,8 +3,11 @@ reference trainer's agent_SPS (clean_pufferl.py:364-376) with the HIP stepper, H
 small stand-in policy, plus the train side (sort, GAE, PPO epochs) per update.
 
 Usage (GPU box): python tools/bench_trainer.py [envs] [batch_size] [updates] [--fused-heads] [--fused-loss]
+                                               [--recurrent] [--fused-lstm]
 (--fused-heads: the agent's action heads run as the fused HIP kernels, nmmo_amd/heads.py;
- --fused-loss: the PPO minibatch loss runs as the fused HIP kernel, nmmo_amd/ppo.py)
+ --fused-loss: the PPO minibatch loss runs as the fused HIP kernel, nmmo_amd/ppo.py;
+ --recurrent: RecurrentMaskedAgent, an LSTM between encoder and heads with one state per agent slot;
+ --fused-lstm: its recurrence runs as the fused HIP kernels, nmmo_amd/lstm.py; implies --recurrent)
 """
 
 import json
@@ -18,13 +21,15 @@ import torch  # noqa: E402
 
 from nmmo_amd.config import Config  # noqa: E402
 from nmmo_amd.engine import NmmoEngine  # noqa: E402
-from nmmo_amd.trainer import DeviceTrainer, MaskedLinearAgent, TrainConfig  # noqa: E402
+from nmmo_amd.trainer import DeviceTrainer, MaskedLinearAgent, RecurrentMaskedAgent, TrainConfig  # noqa: E402
 
 
 def main():
     fused = "--fused-heads" in sys.argv
     fused_loss = "--fused-loss" in sys.argv
-    argv = [a for a in sys.argv if a not in ("--fused-heads", "--fused-loss")]
+    fused_lstm = "--fused-lstm" in sys.argv
+    recurrent = fused_lstm or "--recurrent" in sys.argv
+    argv = [a for a in sys.argv if not a.startswith("--")]
     envs = int(argv[1]) if len(argv) > 1 else 64
     batch = int(argv[2]) if len(argv) > 2 else 32768
     updates = int(argv[3]) if len(argv) > 3 else 3
@@ -32,7 +37,10 @@ def main():
     cfg = Config.preset("C4", early_stop_agent_num=8)
     eng = NmmoEngine(cfg, envs, seed=1)
     eng.reset()
-    agent = MaskedLinearAgent(cfg.TASK_EMBED_DIM, fused_heads=fused, seed=1).cuda()
+    if recurrent:
+        agent = RecurrentMaskedAgent(cfg.TASK_EMBED_DIM, fused_heads=fused, seed=1, fused_lstm=fused_lstm).cuda()
+    else:
+        agent = MaskedLinearAgent(cfg.TASK_EMBED_DIM, fused_heads=fused, seed=1).cuda()
     tc = TrainConfig(batch_size=batch, total_timesteps=batch * (updates + 1), fused_loss=fused_loss)
     tr = DeviceTrainer(eng, agent, tc)
     tr.evaluate()  # warm-up (allocator, kernels)
@@ -42,10 +50,13 @@ def main():
         ev.append(tr.evaluate())
         trn.append(tr.train())
     out = {
-        "workload": f"C4 {envs} envs x 128 agents, flat obs, batch_size {batch}, MaskedLinearAgent"
-                    + (", fused heads" if fused else "") + (", fused loss" if fused_loss else ""),
+        "workload": f"C4 {envs} envs x 128 agents, flat obs, batch_size {batch}, {type(agent).__name__}"
+                    + (", fused heads" if fused else "") + (", fused loss" if fused_loss else "")
+                    + (", fused lstm" if fused_lstm else ""),
         "fused_heads": fused,
         "fused_loss": fused_loss,
+        "recurrent": recurrent,
+        "fused_lstm": fused_lstm,
         "agent_SPS": round(sum(e["agent_SPS"] for e in ev) / len(ev)),
         "SPS": round(sum(e["SPS"] for e in ev) / len(ev)),
         "eval_time_s": round(sum(e["eval_time"] for e in ev) / len(ev), 4),
