@@ -1,8 +1,5 @@
-"""Loader for libnmmo_hip.so (the HIP path). Fails loudly: there is no CPU fallback.
-
-torch is imported first so that the library's libamdhip64.so.7 dependency binds to the HIP
-runtime torch already loaded (one runtime per process: device pointers from the torch caching
-allocator and streams from torch.cuda are then valid inside the library).
+"""Loader for libnmmo_hip.so (the HIP path). Fails loudly: there is no CPU fallback. `_loader`
+imports torch first, so that the library binds to the HIP runtime torch loaded.
 """
 
 from __future__ import annotations
@@ -10,11 +7,9 @@ from __future__ import annotations
 import ctypes
 import os
 
-from . import abi
+from . import _loader, abi, build
 
-_PKG = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get(
-    "NMMO_LIB", os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libnmmo_hip.so"))
+LIB_PATH = os.environ.get("NMMO_LIB", build.LIB_PATH)
 _lib = None
 
 SYMBOLS = [
@@ -43,24 +38,9 @@ def lib():
     global _lib
     if _lib is not None:
         return _lib
-    import torch  # noqa: F401  (bind the HIP runtime torch ships, see module docstring)
-
-    if not os.path.exists(LIB_PATH):
-        raise NativeError(
-            f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`"
-            " (there is no CPU fallback for the HIP stepper)")
-    L = declare(ctypes.CDLL(LIB_PATH))
+    L = _loader.load("hip", LIB_PATH, NativeError, "nmmo", declare, "there is no CPU fallback for the HIP stepper")
     if L.nmmo_abi_version() != abi.ABI_VERSION:
         raise NativeError(f"ABI mismatch: lib {L.nmmo_abi_version()} != python {abi.ABI_VERSION}")
-    info = build_info(L)
-    if os.environ.get("NMMO_ALLOW_STALE") != "1" and os.path.isdir(os.path.join(_PKG, "csrc")):
-        from .build import source_hash
-
-        want = source_hash()
-        if info.get("src") != want:
-            raise NativeError(
-                f"{LIB_PATH} was built from other sources (src={info.get('src')}, tree={want}): "
-                "rebuild it (`python -m nmmo_amd.build --force`)")
     _lib = L
     return L
 
@@ -145,8 +125,7 @@ def declare(L):
 
 def build_info(L=None) -> dict:
     """nmmo_build_info() as a dict (src = source hash the library was compiled from)."""
-    L = lib() if L is None else L
-    return dict(kv.split("=", 1) for kv in L.nmmo_build_info().decode().split() if "=" in kv)
+    return _loader.build_info(lib() if L is None else L, "nmmo")
 
 
 def check(rc: int, what: str):

@@ -3,35 +3,19 @@
 // stream, never synchronises inside nmmo_step (graph-capturable, no allocation).
 #include <math.h>
 #include <stdlib.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
 #include <map>
 #include <mutex>
-#include <string>
 #include <vector>
 
+#include "host_api.h"
 #include "kernels.h"
 #include "wire.h"
 
-
-
 using namespace nmmo;
 
-static thread_local std::string g_err;
-
-static int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-static int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return code;
-}
 #define HIP_TRY(expr)                                                                    \
   do {                                                                                   \
     hipError_t _e = (expr);                                                              \
@@ -118,11 +102,8 @@ static float half_to_float(uint16_t h) {
 extern "C" {
 
 int32_t nmmo_abi_version(void) { return NMMO_ABI_VERSION; }
-#ifndef NMMO_SRC_HASH
-#define NMMO_SRC_HASH "unknown"
-#endif
 const char* nmmo_build_info(void) {
-  return "src=" NMMO_SRC_HASH " arch=gfx950 fp_contract=off"
+  return NMMO_BUILD_INFO
 #ifdef NMMO_STAMPS
          " stamps=1"
 #endif

@@ -14,13 +14,11 @@
 // and stores are coalesced dwords (rows are not 16-byte aligned: the flat obs row stride is
 // 23,987 floats, a logits row 1,586).
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include <algorithm>
-#include <string>
 
 #include "common.h"
+#include "host_api.h"
 #include "../../include/nmmo_heads.h"
 
 using namespace nmmo;
@@ -224,19 +222,6 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void nmh_backward_kernel(
   }
 }
 
-thread_local std::string g_err;
-
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int code, const char* fmt, ...) {
-  char buf[256];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return code;
-}
-
 // the argument checks both entry points share; *total gets sum(dims)
 int check_args(const char* fn, const NmhHeads* hd, int32_t n_rows, const void* logits, int64_t ls, const void* mask,
                int64_t ms, int32_t mask_kind, int64_t* total) {
@@ -269,10 +254,7 @@ int launched(const char* fn) {
 extern "C" {
 
 const char* nmh_last_error(void) { return g_err.c_str(); }
-#ifndef NMH_SRC_HASH
-#define NMH_SRC_HASH "unknown"
-#endif
-const char* nmh_build_info(void) { return "src=" NMH_SRC_HASH " arch=gfx950 fp_contract=off"; }
+const char* nmh_build_info(void) { return NMMO_BUILD_INFO; }
 
 int nmh_forward(const NmhHeads* hd, int32_t n_rows, const float* logits, int64_t logits_stride, const void* mask,
                 int64_t mask_stride, int32_t mask_kind, const int32_t* actions_in, uint64_t seed, uint64_t offset,

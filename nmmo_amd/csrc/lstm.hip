@@ -18,11 +18,8 @@
 // so results are bit-identical from run to run.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 
-#include <string>
-
+#include "host_api.h"
 #include "../../include/nmmo_lstm.h"
 
 namespace {
@@ -332,19 +329,6 @@ size_t backward_lds(int H) {
   return (size_t)kRows * 4 * H * sizeof(float) + (S > 1 ? (size_t)S * kRows * H * sizeof(double) : 0);
 }
 
-thread_local std::string g_err;
-
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int code, const char* fmt, ...) {
-  char buf[256];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return code;
-}
-
 // 0, or the error of a call named `fn` whose B, H (and T, when has_t) are out of range
 int check_shape(const char* fn, bool has_t, int T, int B, int H) {
   if (has_t && (T < 1 || T > NML_MAX_T)) return fail(NML_E_INVALID, "%s: T %d outside 1..%d", fn, T, NML_MAX_T);
@@ -378,10 +362,7 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 
 extern "C" {
 
 const char* nml_last_error(void) { return g_err.c_str(); }
-#ifndef NML_SRC_HASH
-#define NML_SRC_HASH "unknown"
-#endif
-const char* nml_build_info(void) { return "src=" NML_SRC_HASH " arch=gfx950 fp_contract=off"; }
+const char* nml_build_info(void) { return NMMO_BUILD_INFO; }
 
 int nml_cell(int32_t B, int32_t H, const float* ga, const float* gb, const float* b_ih, const float* b_hh,
              const float* c_prev, float* h_out, float* c_out, float* gates_out, void* stream) {

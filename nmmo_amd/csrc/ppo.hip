@@ -13,12 +13,10 @@
 // output is rounded to float32 once.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include <cmath>
-#include <string>
 
+#include "host_api.h"
 #include "../../include/nmmo_ppo.h"
 
 namespace {
@@ -185,19 +183,6 @@ __global__ __launch_bounds__(kThreads) void nmp_loss_kernel(NmpParams p, int n, 
   }
 }
 
-thread_local std::string g_err;
-
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int code, const char* fmt, ...) {
-  char buf[256];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return code;
-}
-
 bool coef_ok(double c) { return std::isfinite(c) && c >= 0.0; }
 
 }  // namespace
@@ -205,10 +190,7 @@ bool coef_ok(double c) { return std::isfinite(c) && c >= 0.0; }
 extern "C" {
 
 const char* nmp_last_error(void) { return g_err.c_str(); }
-#ifndef NMP_SRC_HASH
-#define NMP_SRC_HASH "unknown"
-#endif
-const char* nmp_build_info(void) { return "src=" NMP_SRC_HASH " arch=gfx950 fp_contract=off"; }
+const char* nmp_build_info(void) { return NMMO_BUILD_INFO; }
 
 int nmp_loss(const NmpParams* params, int32_t n, const float* newlogprob, const float* entropy, const float* newvalue,
              const float* old_logprob, const float* advantages, const float* returns, const float* old_values,

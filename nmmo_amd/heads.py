@@ -9,7 +9,7 @@ policies (baseline_policy.py:245-262) by one kernel forward and one backward. Th
 fallback: a missing or stale library is an error.
 
 torch is imported first so that the library binds to the HIP runtime torch loaded (see
-`_native.py`): tensors' device pointers and torch's streams are then valid inside the library.
+`_loader.py`): tensors' device pointers and torch's streams are then valid inside the library.
 """
 
 from __future__ import annotations
@@ -17,8 +17,9 @@ from __future__ import annotations
 import ctypes
 import os
 
-_PKG = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("NMMO_HEADS_LIB", os.path.join(_PKG, "lib", "libnmmo_heads.so"))
+from . import _loader, build
+
+LIB_PATH = os.environ.get("NMMO_HEADS_LIB", build.lib_path("heads"))
 SYMBOLS = ["nmh_forward", "nmh_backward", "nmh_last_error", "nmh_build_info"]
 MAX_HEADS, MAX_DIM = 16, 2048
 MASK_F32, MASK_U8 = 0, 1
@@ -34,34 +35,19 @@ class NmhHeads(ctypes.Structure):
     _fields_ = [("n_heads", ctypes.c_int32), ("dims", ctypes.c_int32 * MAX_HEADS)]
 
 
-def lib():
-    global _lib
-    if _lib is not None:
-        return _lib
-    import torch  # noqa: F401  (bind the HIP runtime torch ships)
-
-    if not os.path.exists(LIB_PATH):
-        raise HeadsError(
-            f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`"
-            " (there is no torch fallback for the fused heads)")
-    L = ctypes.CDLL(LIB_PATH)
+def declare(L):
     vp, i32, i64, u64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
     hp = ctypes.POINTER(NmhHeads)
     L.nmh_forward.argtypes = [hp, i32, vp, i64, vp, i64, i32, vp, u64, u64, ctypes.c_uint32, vp, vp, vp, vp, vp, vp]
     L.nmh_backward.argtypes = [hp, i32, vp, i64, vp, i64, i32, vp, vp, vp, vp, vp, vp, i64, vp]
-    L.nmh_last_error.restype = ctypes.c_char_p
-    L.nmh_build_info.restype = ctypes.c_char_p
-    if os.environ.get("NMMO_ALLOW_STALE") != "1" and os.path.isdir(os.path.join(_PKG, "csrc")):
-        from .build import heads_source_hash
 
-        info = dict(kv.split("=", 1) for kv in L.nmh_build_info().decode().split() if "=" in kv)
-        want = heads_source_hash()
-        if info.get("src") != want:
-            raise HeadsError(
-                f"{LIB_PATH} was built from other sources (src={info.get('src')}, tree={want}): "
-                "rebuild it (`python -m nmmo_amd.build --force`)")
-    _lib = L
-    return L
+
+def lib():
+    global _lib
+    if _lib is None:
+        _lib = _loader.load("heads", LIB_PATH, HeadsError, "nmh", declare,
+                            "there is no torch fallback for the fused heads")
+    return _lib
 
 
 def check(rc: int, what: str):

@@ -15,7 +15,7 @@ decides, not a size. There is no torch fallback: a missing or stale library is a
 a host tensor.
 
 torch is imported first so that the library binds to the HIP runtime torch loaded (see
-`_native.py`): tensors' device pointers and torch's streams are then valid inside the library.
+`_loader.py`): tensors' device pointers and torch's streams are then valid inside the library.
 """
 
 from __future__ import annotations
@@ -27,8 +27,9 @@ import os
 import torch
 from torch import nn
 
-_PKG = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("NMMO_LSTM_LIB", os.path.join(_PKG, "lib", "libnmmo_lstm.so"))
+from . import _loader, build
+
+LIB_PATH = os.environ.get("NMMO_LSTM_LIB", build.lib_path("lstm"))
 SYMBOLS = ["nml_cell", "nml_seq_forward", "nml_seq_backward", "nml_last_error", "nml_build_info"]
 NML_OK, NML_E_INVALID, NML_E_HIP = 0, -1, -2
 H_STEP, MAX_H, MAX_B, MAX_T = 64, 1024, 1 << 24, 4096
@@ -40,32 +41,19 @@ class LstmError(RuntimeError):
     pass
 
 
-def lib():
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise LstmError(
-            f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`"
-            " (there is no torch fallback for the fused LSTM)")
-    L = ctypes.CDLL(LIB_PATH)
+def declare(L):
     vp, i32 = ctypes.c_void_p, ctypes.c_int32
     L.nml_cell.argtypes = [i32, i32] + [vp] * 9
     L.nml_seq_forward.argtypes = [i32, i32, i32] + [vp] * 12
     L.nml_seq_backward.argtypes = [i32, i32, i32] + [vp] * 11
-    L.nml_last_error.restype = ctypes.c_char_p
-    L.nml_build_info.restype = ctypes.c_char_p
-    if os.environ.get("NMMO_ALLOW_STALE") != "1" and os.path.isdir(os.path.join(_PKG, "csrc")):
-        from .build import lstm_source_hash
 
-        info = dict(kv.split("=", 1) for kv in L.nml_build_info().decode().split() if "=" in kv)
-        want = lstm_source_hash()
-        if info.get("src") != want:
-            raise LstmError(
-                f"{LIB_PATH} was built from other sources (src={info.get('src')}, tree={want}): "
-                "rebuild it (`python -m nmmo_amd.build --force`)")
-    _lib = L
-    return L
+
+def lib():
+    global _lib
+    if _lib is None:
+        _lib = _loader.load("lstm", LIB_PATH, LstmError, "nml", declare,
+                            "there is no torch fallback for the fused LSTM")
+    return _lib
 
 
 def check(rc: int, what: str):

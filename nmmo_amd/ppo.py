@@ -11,7 +11,7 @@ also leaves the gradients with respect to newlogprob, entropy and newvalue; back
 them. There is no torch fallback: a missing or stale library is an error.
 
 torch is imported first so that the library binds to the HIP runtime torch loaded (see
-`_native.py`): tensors' device pointers and torch's streams are then valid inside the library.
+`_loader.py`): tensors' device pointers and torch's streams are then valid inside the library.
 """
 
 from __future__ import annotations
@@ -19,8 +19,9 @@ from __future__ import annotations
 import ctypes
 import os
 
-_PKG = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("NMMO_PPO_LIB", os.path.join(_PKG, "lib", "libnmmo_ppo.so"))
+from . import _loader, build
+
+LIB_PATH = os.environ.get("NMMO_PPO_LIB", build.lib_path("ppo"))
 SYMBOLS = ["nmp_loss", "nmp_last_error", "nmp_build_info"]
 NMP_OK, NMP_E_INVALID, NMP_E_HIP = 0, -1, -2
 MAX_N = 1 << 24
@@ -39,32 +40,16 @@ class NmpParams(ctypes.Structure):
                 ("vf_coef", ctypes.c_double), ("norm_adv", ctypes.c_int32), ("clip_vloss", ctypes.c_int32)]
 
 
+def declare(L):
+    L.nmp_loss.argtypes = [ctypes.POINTER(NmpParams), ctypes.c_int32] + [ctypes.c_void_p] * 14
+
+
 def lib():
     global _lib
-    if _lib is not None:
-        return _lib
-    import torch  # noqa: F401  (bind the HIP runtime torch ships)
-
-    if not os.path.exists(LIB_PATH):
-        raise PpoError(
-            f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`"
-            " (there is no torch fallback for the fused loss)")
-    L = ctypes.CDLL(LIB_PATH)
-    vp = ctypes.c_void_p
-    L.nmp_loss.argtypes = [ctypes.POINTER(NmpParams), ctypes.c_int32] + [vp] * 14
-    L.nmp_last_error.restype = ctypes.c_char_p
-    L.nmp_build_info.restype = ctypes.c_char_p
-    if os.environ.get("NMMO_ALLOW_STALE") != "1" and os.path.isdir(os.path.join(_PKG, "csrc")):
-        from .build import ppo_source_hash
-
-        info = dict(kv.split("=", 1) for kv in L.nmp_build_info().decode().split() if "=" in kv)
-        want = ppo_source_hash()
-        if info.get("src") != want:
-            raise PpoError(
-                f"{LIB_PATH} was built from other sources (src={info.get('src')}, tree={want}): "
-                "rebuild it (`python -m nmmo_amd.build --force`)")
-    _lib = L
-    return L
+    if _lib is None:
+        _lib = _loader.load("ppo", LIB_PATH, PpoError, "nmp", declare,
+                            "there is no torch fallback for the fused loss")
+    return _lib
 
 
 def check(rc: int, what: str):

@@ -1,6 +1,7 @@
 """Diagnostic A/B helper: build the library from the sources of a git revision (default HEAD) into
 nmmo_amd/lib/libnmmo_hip_<name>.so (NMMO_SRC_HASH "var-<name>"; load with NMMO_ALLOW_STALE=1).
-Only the revision's files named in build.SOURCES are compiled (heads.hip is a library of its own).
+Only the revision's files named in build.SOURCES are compiled: the product library's row of
+build.LIBS (the other rows are libraries of their own).
 Usage: python tools/debug/build_rev.py <name> [rev]"""
 import os
 import subprocess
