@@ -349,7 +349,7 @@ NMMO_API int nmmo_obs_invalidate_envs(NmmoHandle* h, const int32_t* env_ids, int
  * forgotten -- the next gather rewrites every Tile entry of those rows (and re-zeroes the Tile of
  * rows out of the realm) and stays incremental everywhere else: what the start-kit policy's
  * in-place edit of Tile[:, :, :2] needs (baseline_policy.py:96-97). Any other mask, or a handle
- * whose rows do not track the Tile section (native layout, slot counts not a multiple of 8),
+ * whose rows do not track the Tile section (native layout),
  * forgets the listed envs' whole rows. env_ids NULL = every env (n_ids ignored). Enqueued on
  * `stream`; capture-safe. */
 #define NMMO_OBS_SEC_TILE 1u

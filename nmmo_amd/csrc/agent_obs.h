@@ -112,24 +112,29 @@ __device__ __forceinline__ void put_field(uint32_t (&img)[kW], uint64_t lo, uint
 // Every load of the thread is in flight before the first LDS write: a load -> write loop waited
 // one memory round trip per 16-B word (6 per thread at S = 384, blockDim 256), and the listings'
 // count -> mlist -> item chain ahead of the stage was three more.
+// kAligned: S % 8 == 0, the columns copied as 16-B words; false takes any S <= kMaxSlots, the columns
+// copied by ao_stage_store in a load -> write loop (the flat rows' kernel at other slot counts).
 constexpr int kAoStageIt = (NMMO_N_ENTITY_COLS * (kMaxSlots / 8) + 255) / 256;
 struct AoStage {
   uint4 x[kAoStageIt];
   int al[2], ds[2];
   int nm, mv;  // the env's listing count (as stored) and listing tid's mlist word (any when >= nm)
 };
+template <bool kAligned = true>
 __device__ __forceinline__ void ao_stage_load(const ObsParams& p, int e, AoStage& r) {
   const int S = p.S, tid = threadIdx.x;
   const int16_t* E = p.ent + (size_t)e * NMMO_NF * S;
-  const int w4 = S / 8;  // 16-B words per field (S % 8 == 0: checked by the launchers)
+  const int w4 = S / 8;  // 16-B words per field (kAligned: S % 8 == 0, checked by the launchers)
   const int nw = NMMO_N_ENTITY_COLS * w4;
   r.nm = p.mcount[e];
   r.mv = p.mlist[(size_t)e * NMMO_MARKET_ROWS + min(tid, NMMO_MARKET_ROWS - 1)];
+  if constexpr (kAligned) {
 #pragma unroll
-  for (int k = 0; k < kAoStageIt; k++) {
-    const int i = tid + (int)blockDim.x * k;
-    const int f = i / w4, j = i - f * w4;
-    r.x[k] = i < nw ? reinterpret_cast<const uint4*>(E + (size_t)f * S)[j] : make_uint4(0u, 0u, 0u, 0u);
+    for (int k = 0; k < kAoStageIt; k++) {
+      const int i = tid + (int)blockDim.x * k;
+      const int f = i / w4, j = i - f * w4;
+      r.x[k] = i < nw ? reinterpret_cast<const uint4*>(E + (size_t)f * S)[j] : make_uint4(0u, 0u, 0u, 0u);
+    }
   }
 #pragma unroll
   for (int u = 0; u < 2; u++) {  // (a clamped slot: a conditional load is waited on at its branch's join)
@@ -138,6 +143,7 @@ __device__ __forceinline__ void ao_stage_load(const ObsParams& p, int e, AoStage
     r.ds[u] = E[F_DS_ROW * S + s];
   }
 }
+template <bool kAligned = true>
 __device__ __forceinline__ void ao_stage_store(const ObsParams& p, int e, int16_t* T, uint32_t* pk, const AoStage& r) {
   const int S = p.S, P = p.P, Sp = ao_stride(S), tid = threadIdx.x;
   const int16_t* E = p.ent + (size_t)e * NMMO_NF * S;
@@ -146,26 +152,33 @@ __device__ __forceinline__ void ao_stage_store(const ObsParams& p, int e, int16_
   constexpr int kIt = kAoStageIt;
   const int(&al)[2] = r.al;
   const int(&ds)[2] = r.ds;
+  if constexpr (kAligned) {
 #pragma unroll
-  for (int k = 0; k < kIt; k++) {
-    const int i = tid + (int)blockDim.x * k;
-    if (i < nw) {
-      const int f = i / w4, j = i - f * w4;
-      uint32_t* d = reinterpret_cast<uint32_t*>(T + f * Sp) + 4 * j;
-      d[0] = r.x[k].x;
-      d[1] = r.x[k].y;
-      d[2] = r.x[k].z;
-      d[3] = r.x[k].w;
+    for (int k = 0; k < kIt; k++) {
+      const int i = tid + (int)blockDim.x * k;
+      if (i < nw) {
+        const int f = i / w4, j = i - f * w4;
+        uint32_t* d = reinterpret_cast<uint32_t*>(T + f * Sp) + 4 * j;
+        d[0] = r.x[k].x;
+        d[1] = r.x[k].y;
+        d[2] = r.x[k].z;
+        d[3] = r.x[k].w;
+      }
     }
-  }
-  for (int i = tid + (int)blockDim.x * kIt; i < nw; i += blockDim.x) {  // (blocks under 256 threads)
-    const int f = i / w4, j = i - f * w4;
-    const uint4 y = reinterpret_cast<const uint4*>(E + (size_t)f * S)[j];
-    uint32_t* d = reinterpret_cast<uint32_t*>(T + f * Sp) + 4 * j;
-    d[0] = y.x;
-    d[1] = y.y;
-    d[2] = y.z;
-    d[3] = y.w;
+    for (int i = tid + (int)blockDim.x * kIt; i < nw; i += blockDim.x) {  // (blocks under 256 threads)
+      const int f = i / w4, j = i - f * w4;
+      const uint4 y = reinterpret_cast<const uint4*>(E + (size_t)f * S)[j];
+      uint32_t* d = reinterpret_cast<uint32_t*>(T + f * Sp) + 4 * j;
+      d[0] = y.x;
+      d[1] = y.y;
+      d[2] = y.z;
+      d[3] = y.w;
+    }
+  } else {  // any S: element by element (no product shape takes this path)
+    for (int i = tid; i < NMMO_N_ENTITY_COLS * S; i += blockDim.x) {
+      const int f = i / S;
+      T[f * Sp + i - f * S] = E[i];
+    }
   }
   for (int k = tid; k < kMaxSlots + 64; k += blockDim.x) pk[k] = kAoEmpty;
   __syncthreads();

@@ -632,9 +632,9 @@ int nmmo_obs_invalidate_sections(NmmoHandle* h, const int32_t* env_ids, int32_t 
   if (n_ids < 0 || n_ids > h->st.n_envs) return fail(NMMO_E_INVALID, "n_ids %d not in 0..%d", n_ids, h->st.n_envs);
   if (!h->d_zrow || n_ids == 0 || sections == 0) return NMMO_OK;
   HIP_TRY(hipSetDevice(h->device));
-  // the Tile section alone is tracked per row by the flat rows of flat_obs.hip (slots a multiple of
-  // 8); any other section, layout or kernel forgets the listed envs' whole rows
-  const bool tile_only = sections == NMMO_OBS_SEC_TILE && h->cfg.obs_layout == NMMO_OBS_FLAT && h->st.S % 8 == 0;
+  // the Tile section alone is tracked per row by the flat rows (flat_obs.hip); any other section or
+  // layout forgets the listed envs' whole rows
+  const bool tile_only = sections == NMMO_OBS_SEC_TILE && h->cfg.obs_layout == NMMO_OBS_FLAT;
   if (!tile_only) {
     if (!env_ids) {
       HIP_TRY(hipMemsetAsync(h->d_zrow, 0, (size_t)h->st.n_envs * h->st.P * 8, (hipStream_t)stream));

@@ -2,8 +2,9 @@
 // incrementally into the handle's bound buffer (nmmo_obs_bind): a row stores only
 // what differs from what the buffer already holds (ObsParams::zrow / zst). Replaces
 // Env._compute_observations + pufferlib's flatten/pad (the rows the reference's learner decodes with
-// unpack_batched_obs, baseline_policy.py:41) for the bound buffer; an unbound or untracked buffer
-// gets every row in full from obs.hip's obs_kernel<kWrap, true>.
+// unpack_batched_obs, baseline_policy.py:41) for the bound buffer, at every slot count; an unbound or
+// untracked buffer gets every row in full from obs.hip's obs_kernel<kWrap>. The row-state protocol
+// (kernels.h kZsZero / kZsExt / kZsTile, zs_pack) has this one reader and writer among the flat rows.
 //
 // Round 5 rewrite on agent_obs.h's pieces (the native kernel's staging, compaction and section bit
 // fields). The round-4 flat kernel was issue-bound (per agent row 760 VALU, 524 SALU, 146 branch
@@ -75,6 +76,9 @@ static_assert(kWireBuyLo / 64 == 1 && (kWireBuyLo + NMMO_MARKET_ROWS) / 64 == 17
 //    barrier nothing reads them -- an agent's own position is kept in a register (my_rc) and a
 //    visible entity's comes from its packed word (ao_row / ao_col: the values the window test used).
 //    A smaller S has smaller columns and LDS to spare: the item words follow the window rows.
+// None of the regions' alignment depends on S: ao_stride(S) is twice an odd number for every S (383
+// shares 384's), T is padded to 16 B, the pool, the visible rows and the window rows are multiples of
+// 16 B, and fo_items_in_T takes the item words into T only where they land 8-B aligned.
 constexpr int kFoVisw = (kNObs + 3) & ~3;            // visible-row words per wave (the compaction writes pos < kNObs)
 constexpr int kFoWinRowBytes = 16, kFoWinAgentBytes = 15 * kFoWinRowBytes;
 constexpr size_t kFoWinBytes = (size_t)kAoAgents * kFoWinAgentBytes, kFoItemBytes = (size_t)kAoAgents * kInv * 8;
@@ -258,7 +262,8 @@ typedef const __attribute__((address_space(4))) ObsParams* FoArgs;  // the kerne
 // kS: the slot count when known at compile time (C3 / C4: 128 players + 256 NPCs), 0 = p.S. With
 // it the staged-column offsets are immediates instead of uniform values the agent loop keeps live.
 // 5 waves per SIMD (5 workgroups of 4 waves per CU): 96 VGPRs, which the kernel fits without scratch.
-template <bool kWrap, int kS>
+// kAligned: S % 8 == 0 (agent_obs.h's 16-B column loads); false stages any S element by element.
+template <bool kWrap, int kS, bool kAligned = true>
 __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per_eu(5, 5))) flat_obs_kernel(ObsParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int S = kS ? kS : p.S, P = p.P, Sp = ao_stride(S), tdim = p.task_dim, elems = kFlatTask + tdim + kTileN;
@@ -289,7 +294,7 @@ __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per
   // agents' extended row state and the workgroup's windows. (Issued where each was first needed,
   // the count -> mlist -> item chain, the stage, the windows and the extended state were six.)
   AoStage sg;
-  ao_stage_load(p, e, sg);
+  ao_stage_load<kAligned>(p, e, sg);
   const int16_t* E = p.ent + (size_t)e * NMMO_NF * S;
   constexpr int kPerWave = kAoAgents / kAoWaves;
   const int abase = g * kAoAgents + w;
@@ -308,7 +313,7 @@ __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per
     if constexpr (kWrap)
       if (p.ws) my_prev = p.ws[ai].prev_price;
   }
-  ao_stage_store(p, e, T, pk, sg);
+  ao_stage_store<kAligned>(p, e, T, pk, sg);
   if (!mine) {
     my_task = 0, my_prev = -1, my_alive = 0;
     my_z = my_s = 0;
@@ -654,12 +659,8 @@ __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per
   }
 }
 
-bool flat_obs_ok(const ObsParams& p) {  // agent_obs.h's staging: S a multiple of 8 (16-B column loads)
-  return p.S % 8 == 0 && p.S <= kMaxSlots && p.P <= 128 && p.obs && p.ztag && p.zrow;
-}
-
 hipError_t launch_flat_obs(const ObsParams& p, hipStream_t stream) {
-  if (!flat_obs_ok(p)) return hipErrorInvalidValue;
+  if (!(p.obs && p.ztag && p.zrow)) return hipErrorInvalidValue;  // a tracked buffer only
   const int ne = list_grid(p.env_list, p.n_list, p.n_envs);
   if (ne <= 0) return hipSuccess;
 #if NMMO_FO_XCD
@@ -671,6 +672,9 @@ hipError_t launch_flat_obs(const ObsParams& p, hipStream_t stream) {
   if (p.S == kMaxSlots) {
     if (p.wflags) hipLaunchKernelGGL((flat_obs_kernel<true, kMaxSlots>), grid, block, lds, stream, p);
     else hipLaunchKernelGGL((flat_obs_kernel<false, kMaxSlots>), grid, block, lds, stream, p);
+  } else if (p.S % 8 != 0) {
+    if (p.wflags) hipLaunchKernelGGL((flat_obs_kernel<true, 0, false>), grid, block, lds, stream, p);
+    else hipLaunchKernelGGL((flat_obs_kernel<false, 0, false>), grid, block, lds, stream, p);
   } else {
     if (p.wflags) hipLaunchKernelGGL((flat_obs_kernel<true, 0>), grid, block, lds, stream, p);
     else hipLaunchKernelGGL((flat_obs_kernel<false, 0>), grid, block, lds, stream, p);

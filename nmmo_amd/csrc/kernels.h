@@ -231,7 +231,6 @@ hipError_t launch_wire_header(const ObsParams& p, hipStream_t s);
 hipError_t launch_wire_obs(const ObsParams& p, hipStream_t s);
 // flat obs rows into the handle's bound buffer, incrementally (flat_obs.hip; p.ztag != 0)
 hipError_t launch_flat_obs(const ObsParams& p, hipStream_t s);
-bool flat_obs_ok(const ObsParams& p);  // launch_flat_obs takes p (else obs_kernel<kWrap, false>)
 // NMMO_OBS_NATIVE obs gather (native_obs.hip)
 hipError_t launch_native_obs(const ObsParams& p, hipStream_t s);
 // header + record-head consistency of a wire buffer; bits into *status (0 = valid)

@@ -126,31 +126,24 @@ __device__ __forceinline__ void mask_sec_f32(const ObsParams& p, const int16_t* 
 // embedding) are issued before the previous agent's remaining ~130 stores (vmcnt retires in
 // issue order, so a load issued after a store stream waits for all of it; issued ahead of >= 63
 // younger stores it costs no wait at all).
-#ifndef NMMO_OBS_TASK_REGS  // (A/B knobs: tools/debug/variants.py)
-#define NMMO_OBS_TASK_REGS 0  // (32 before the Task section was kept across steps: 156 VGPRs)
-#endif
-// Task embedding dwords per lane held in registers (2,048 per row): the incremental variant writes
-// a Task section once per episode and reads it in place; the full-write variant (every row every
-// launch: an unbound or untracked buffer, NMMO_OBS_REZERO) prefetches its first 2,048 floats with
-// the agent's other loads, so its Task stores never wait behind the Tile stores issued before them.
+// Task embedding dwords per lane held in registers (2,048 per row): the first 2,048 floats are
+// prefetched with the agent's other loads, so the Task stores never wait behind the Tile stores
+// issued before them.
 #ifndef NMMO_OBS_FULL_TREGS  // (A/B knobs: 0 and 4 = the round-4 full write)
 #define NMMO_OBS_FULL_TREGS 32
 #endif
 #ifndef NMMO_OBS_FULL_WPE
 #define NMMO_OBS_FULL_WPE 3
 #endif
-constexpr int kTaskRegsFull = NMMO_OBS_FULL_TREGS;
+constexpr int kTaskRegs = NMMO_OBS_FULL_TREGS;
 
-// kWrap: the wrapper's observation() edits are compiled in (SPEC §13). kFull: no row state (every
-// row written in full, Task from registers); 3 waves per SIMD (the registers take it past 128).
-#ifndef NMMO_OBS_WPE  // 4 waves per SIMD: the wrapper variant would take 129 VGPRs (3 waves) and
-#define NMMO_OBS_WPE 4  // fits 128 with a 20-B spill instead; the plain one is 128 either way
-#endif
-template <bool kWrap, bool kFull>
-__global__ void __launch_bounds__(64 * kFlatWaves)
-__attribute__((amdgpu_waves_per_eu(kFull ? NMMO_OBS_FULL_WPE : NMMO_OBS_WPE, kFull ? NMMO_OBS_FULL_WPE : NMMO_OBS_WPE)))
+// Every row in full, no row state read or written: an unbound or untracked buffer (p.ztag == 0:
+// observe(out=...), NMMO_OBS_REZERO); the bound buffer's incremental rows are flat_obs.hip's.
+// kWrap: the wrapper's observation() edits are compiled in (SPEC §13). 3 waves per SIMD (the Task
+// registers take it past 128).
+template <bool kWrap>
+__global__ void __launch_bounds__(64 * kFlatWaves) __attribute__((amdgpu_waves_per_eu(NMMO_OBS_FULL_WPE, NMMO_OBS_FULL_WPE)))
 obs_kernel(ObsParams p) {
-  constexpr int kTaskRegs = kFull ? kTaskRegsFull : NMMO_OBS_TASK_REGS;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int S = p.S, elems = flat_elems(p.task_dim);
   int16_t* T = reinterpret_cast<int16_t*>(smem);
@@ -212,28 +205,12 @@ obs_kernel(ObsParams p) {
   constexpr int kPerWave = kFlatAgents / kFlatWaves;
   const int abase = g * kFlatAgents + w;
   int my_task = 0, my_prev = -1;
-  // the row's state (ObsParams::zrow / zst): its Entity rows >= hv, its Market rows and
-  // Buy.MarketItem entries >= hm are zero already (my_h = hv | hm << 12; a row of unknown content:
-  // nothing is known zero, an all-zero row: everything)
-  int my_h = kNObs | NMMO_MARKET_ROWS << 12;
-  bool zv = false, zz = false, zt = false;
   if (lane < kPerWave && abase + kFlatWaves * lane < p.P) {
     const size_t ai = (size_t)e * p.P + abase + kFlatWaves * lane;
     my_task = p.assign[ai];
-    if (p.ztag && p.zrow[ai] == p.ztag) {
-      const uint64_t zs = p.zst[ai];
-      zv = true;
-      zz = (zs & kZsZero) != 0;
-      zt = !zz && zs_task(zs) == my_task;
-      my_h = zz ? 0 : zs_hv(zs) | zs_hm(zs) << 12;
-    }
     if constexpr (kWrap)
       if (p.ws) my_prev = p.ws[ai].prev_price;
   }
-  // bit j: agent j's row state describes this buffer / the row is all-zero / its Task section
-  // holds agent j's task embedding already
-  const uint64_t zvalid = __ballot(zv), zzero = __ballot(zz), zknown_task = __ballot(zt);
-  auto task_known = [&](int j) { return ((zknown_task >> j) & 1) != 0; };
   int nrows = 0;             // rows this wave wrote (rows_out[0])
   unsigned long long nbytes = 0;  // bytes this wave stored (rows_out[1])
   // Entity.Query.window: ascending datastore rows within L-inf <= 7, first 100 -> vis, returns nv
@@ -271,7 +248,7 @@ obs_kernel(ObsParams p) {
       const int t = lane + 64 * i;
       wm[i] = t < 225 ? mat[(r + t / 15 - kVision) * kSize + c + t % 15 - kVision] : 0u;
     }
-    if (treg && !task_known(j)) {
+    if (treg) {
       const float* temb = p.task + (size_t)__builtin_amdgcn_readlane(my_task, j) * p.task_dim + lane;
 #pragma unroll
       for (int i = 0; i < kTaskRegs; i++) tv[i] = temb[64 * i];
@@ -287,31 +264,13 @@ obs_kernel(ObsParams p) {
     const int a = abase + kFlatWaves * j;
     if (a >= p.P) break;
     float* row = p.obs + ((size_t)e * p.P + a) * elems;
-    const bool zv = (zvalid >> j) & 1;
-    const int hj = __builtin_amdgcn_readlane(my_h, j);
-    const int hv = hj & 4095, hm = hj >> 12;
+    nrows++;
+    nbytes += 4ull * elems;
     if (!T[F_ALIVE * S + a]) {  // not in the realm: an all-zero row
       if (alive(j + 1)) prefetch(a + kFlatWaves, j + 1);  // ahead of this row's stores
-      if ((zzero >> j) & 1) continue;  // zeroed by an earlier launch into this buffer
-      if (zv) {  // zero what the last write left nonzero
-        wave_zero(row, 0, kFlatEntity + hv * NMMO_N_ENTITY_COLS);
-        wave_zero(row, kFlatInv, kFlatMarket + hm * kItemCols);
-        wave_zero(row, kFlatTask, elems);
-        nbytes += 4ull * (kFlatEntity + hv * NMMO_N_ENTITY_COLS + kFlatMarket + hm * kItemCols - kFlatInv +
-                          elems - kFlatTask);
-      } else {
-        wave_zero(row, 0, elems);
-        nbytes += 4ull * elems;
-      }
-      if (p.ztag && lane == 0) {
-        p.zrow[(size_t)e * p.P + a] = p.ztag;
-        p.zst[(size_t)e * p.P + a] = kZsZero;
-      }
-      nrows++;
+      wave_zero(row, 0, elems);
       continue;
     }
-    nrows++;
-    const bool tknown = task_known(j);
     m.a = a;
     m.r = T[F_ROW * S + a];
     m.c = T[F_COL * S + a];
@@ -343,10 +302,8 @@ obs_kernel(ObsParams p) {
     m.ninv = inv_count(inv);
     m.prev_price = kWrap ? __builtin_amdgcn_readlane(my_prev, j) : -1;
     const int aid = T[F_ID * S + a];
-    // Task (from registers; a task_dim beyond kTaskRegs * 64 reads the rest directly), unless the
-    // row holds this task's embedding already
-    if (!tknown) {
-      nbytes += 4ull * p.task_dim;
+    // Task (from registers; a task_dim beyond kTaskRegs * 64 reads the rest directly)
+    {
       const int k0 = treg ? kTaskRegs * 64 : 0;  // a shorter embedding is read in place
       if (treg) {
         float* dst = row + kFlatTask + lane;
@@ -361,13 +318,11 @@ obs_kernel(ObsParams p) {
     // ActionTargets, section by section
     mask_sec_f32<0, kWrap>(p, T, S, vis, inv, mpo, nm, m, row);
     mask_sec_f32<1, kWrap>(p, T, S, vis, inv, mpo, nm, m, row);
-    {  // Buy.MarketItem: the listings' entries, the zero entries up to hm, and the no-op entry
-      const int n = max(nm, hm);
-      for (int k = lane; k < n; k += 64)
-        obs_st(&row[kWireBuyLo + k], mask_value<kWrap>(p, T, S, vis, inv, mpo, nm, m, 2, k) ? 1.f : 0.f);
-      if (lane == 0) obs_st(&row[kWireBuyLo + NMMO_MARKET_ROWS], 1.f);
-      nbytes += 4ull * (kFlatId + 2 - NMMO_MARKET_ROWS + n);  // every mask but Buy's tail, id, tick
-    }
+    // Buy.MarketItem: the listings' entries, a zero run to the section's end, and the no-op entry
+    for (int k = lane; k < nm; k += 64)
+      obs_st(&row[kWireBuyLo + k], mask_value<kWrap>(p, T, S, vis, inv, mpo, nm, m, 2, k) ? 1.f : 0.f);
+    wave_zero(row, kWireBuyLo + nm, kWireBuyLo + NMMO_MARKET_ROWS);
+    if (lane == 0) obs_st(&row[kWireBuyLo + NMMO_MARKET_ROWS], 1.f);
     mask_sec_f32<3, kWrap>(p, T, S, vis, inv, mpo, nm, m, row);
     mask_sec_f32<4, kWrap>(p, T, S, vis, inv, mpo, nm, m, row);
     mask_sec_f32<5, kWrap>(p, T, S, vis, inv, mpo, nm, m, row);
@@ -390,13 +345,7 @@ obs_kernel(ObsParams p) {
         if (f < NMMO_N_ENTITY_COLS)
           obs_st(&row[kFlatEntity + k * NMMO_N_ENTITY_COLS + f], k < m.nv ? (float)T[f * S + vis[k]] : 0.f);
       }
-      const int hz = max(nv2, hv);  // the rows past the visible ones not known zero
-      wave_zero(row, kFlatEntity + nv2 * NMMO_N_ENTITY_COLS, kFlatEntity + hz * NMMO_N_ENTITY_COLS);
-      nbytes += 4ull * (hz * NMMO_N_ENTITY_COLS + kInv * kItemCols + max(nm, hm) * kItemCols + kTileN);
-      if (p.ztag && lane == 0) {
-        if (!zv) p.zrow[(size_t)e * p.P + a] = p.ztag;
-        p.zst[(size_t)e * p.P + a] = zs_pack(nv2, nm, __builtin_amdgcn_readlane(my_task, j));
-      }
+      wave_zero(row, kFlatEntity + nv2 * NMMO_N_ENTITY_COLS, kFlatInv);
     }
     // Inventory (own items, owner = self) and Market (env listings, ascending row)
     for (int k = lane; k < kInv * kItemCols; k += 64) {
@@ -405,7 +354,7 @@ obs_kernel(ObsParams p) {
     }
     for (int k = lane; k < nm * kItemCols; k += 64)
       obs_st(&row[kFlatMarket + k], item_col(mitem[k >> 4], (mpo[k >> 4] >> 8) + 1, k & 15));
-    wave_zero(row, kFlatMarket + nm * kItemCols, kFlatMarket + max(nm, hm) * kItemCols);
+    wave_zero(row, kFlatMarket + nm * kItemCols, kFlatTask);
     __builtin_amdgcn_wave_barrier();
   }
   if (p.rows_out && lane == 0 && nrows) {  // per env: one address per env keeps the atomics uncontended
@@ -417,6 +366,7 @@ obs_kernel(ObsParams p) {
 hipError_t launch_obs(const ObsParams& p, hipStream_t stream) {
   if (p.wire) return launch_wire_obs(p, stream);  // wire_obs.hip
   if (p.nat) return launch_native_obs(p, stream);  // native_obs.hip
+  if (p.ztag) return launch_flat_obs(p, stream);  // the bound buffer: incremental rows (flat_obs.hip)
   const int ne = list_grid(p.env_list, p.n_list, p.n_envs);
   if (ne <= 0) return hipSuccess;
 #ifdef NMMO_OBS_XCD
@@ -425,17 +375,8 @@ hipError_t launch_obs(const ObsParams& p, hipStream_t stream) {
   const dim3 grid(ne, (p.P + kFlatAgents - 1) / kFlatAgents), block(64 * kFlatWaves);
 #endif
   const size_t lds = obs_lds_bytes(p.S);
-  if (p.ztag) {  // the bound buffer: incremental rows (flat_obs.hip; here the round-4 kernel for slot
-                 // counts that are not a multiple of 8, and under NMMO_FLAT_V1)
-#ifndef NMMO_FLAT_V1
-    if (flat_obs_ok(p)) return launch_flat_obs(p, stream);
-#endif
-    if (p.wflags) hipLaunchKernelGGL((obs_kernel<true, false>), grid, block, lds, stream, p);
-    else hipLaunchKernelGGL((obs_kernel<false, false>), grid, block, lds, stream, p);
-  } else {  // every row in full
-    if (p.wflags) hipLaunchKernelGGL((obs_kernel<true, true>), grid, block, lds, stream, p);
-    else hipLaunchKernelGGL((obs_kernel<false, true>), grid, block, lds, stream, p);
-  }
+  if (p.wflags) hipLaunchKernelGGL(obs_kernel<true>, grid, block, lds, stream, p);
+  else hipLaunchKernelGGL(obs_kernel<false>, grid, block, lds, stream, p);
   return hipGetLastError();
 }
 

@@ -38,6 +38,8 @@ changing that line's value in a scratch build, the walk then failed where said:
   nmmo_wire_unpack's 1,024 Buy entries: "unpack(wire) vs native" at steps 1, 7..9, 11..13;
   expand_kernel, wire_expand_kernel, record_gather_kernel: test_stores_of_full_rows."""
 
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -300,14 +302,19 @@ def test_stores_of_full_rows():
         e.close()
 
 
-# (13, 3): S = 16 is a multiple of 8, so the incremental kernel runs with one partial group;
-# (13, 4): S = 17 is not, so the full-write obs_kernel fallback runs.
-@pytest.mark.parametrize("P,NPC,out", [(100, 50, tuple(range(16, 32)) + tuple(range(96, 100))),
-                                       (13, 3, (1, 5, 9, 12)), (13, 4, (1, 5, 9, 12))])
+_odd_pair = functools.lru_cache(None)(sc.saturated_pair)  # (the blobs are only read)
+# The slot counts that are no multiple of 8 (flat_obs_kernel<*, 0, false>: the Entity columns staged
+# element by element): (13, 4), S = 17, one partial obs group per env; (100, 50), S = 150, a partial
+# last group, seven workgroups per env and three datastore-row words per lane.
+UNALIGNED = [(13, 4, (1, 5, 9, 12)), (100, 50, tuple(range(16, 32)) + tuple(range(96, 100)))]
+
+
+# (13, 3): S = 16 is a multiple of 8 (flat_obs_kernel<*, 0>) with one partial group
+@pytest.mark.parametrize("P,NPC,out", [UNALIGNED[1], (13, 3, (1, 5, 9, 12)), UNALIGNED[0]])
 def test_saturated_and_shrink_at_odd_sizes(P, NPC, out, monkeypatch):
-    """S != 384 (flat_obs_kernel<*, 0>), a partial last obs group, and a slot count the incremental
-    kernel refuses: saturated, the group out of the realm, saturated again -- flat vs the oracle."""
-    sat, shrunk = sc.saturated_pair(P, NPC, out)
+    """S != 384, a partial last obs group, and slot counts that are no multiple of 8: saturated, the
+    group out of the realm, saturated again -- flat (tracked and under NMMO_OBS_REZERO) vs the oracle."""
+    sat, shrunk = _odd_pair(P, NPC, out)
     flat, rez = _flat_pair(monkeypatch, P, NPC)
     orc = sc.make_oracle(sc.config(P, NPC))
     for name, blob in (("saturated", sat), ("shrunk", shrunk), ("back", sat)):
@@ -318,5 +325,59 @@ def test_saturated_and_shrink_at_odd_sizes(P, NPC, out, monkeypatch):
             h.observe()
             _same(h.obs, want, f"P={P} N={NPC} {name}")
             assert h.get_fault() == 0
+    flat.close()
+    rez.close()
+
+
+@pytest.mark.parametrize("P,NPC,out", UNALIGNED)
+def test_repeated_state_stores_less_at_unaligned_slot_counts(P, NPC, out):
+    """test_repeated_state_stores_less's flat half where S is no multiple of 8: the second observe()
+    of an unchanged state leaves the buffer byte-identical and stores strictly fewer bytes than the
+    first (which zeroes the rows of `out`), so the incremental kernel serves these shapes."""
+    before, blob = _odd_pair(P, NPC, out)
+    eng = _engine(abi.OBS_FLAT, P, NPC)
+    rows = torch.zeros((N, 2), dtype=torch.int64, device=eng.device)
+    eng.set_state(before)
+    eng.observe()
+    eng.set_obs_counter(rows)
+    eng.set_state(blob)
+    eng.observe()
+    first = int(rows[:, 1].sum().item())
+    snap = eng.obs.clone()
+    eng.set_state(blob)
+    eng.observe()
+    second = int(rows[:, 1].sum().item()) - first
+    print(f"P={P} NPC={NPC}: first {first} B, second {second} B, full write {N * P * eng.obs_elems * 4} B")
+    assert torch.equal(eng.obs.view(torch.uint8), snap.view(torch.uint8))
+    assert 0 < second < first, (first, second)
+    assert eng.get_fault() == 0
+    eng.close()
+
+
+@pytest.mark.parametrize("P,NPC,out", UNALIGNED)
+def test_tile_invalidate_repairs_scribbles_at_unaligned_slot_counts(P, NPC, out, monkeypatch):
+    """test_scribble_in_a_zero_row_is_repaired_after_tile_invalidate where S is no multiple of 8, on
+    a row that has just left the realm and on one still in it: after the Tile sections are
+    invalidated the tracked buffer equals the NMMO_OBS_REZERO handle's and the oracle's rows."""
+    sat, shrunk = _odd_pair(P, NPC, out)
+    flat, rez = _flat_pair(monkeypatch, P, NPC)
+    for blob in (sat, shrunk):
+        for h in (flat, rez):
+            h.set_state(blob)
+            h.observe()
+    alive = split_state(shrunk, N, P + NPC, P)["ent"][0, abi.F["alive"], :P] != 0
+    a_out, a_in = out[-1], next(a for a in range(P) if alive[a] and a not in out)
+    assert not alive[a_out] and not bool(flat.obs[0, a_out].any()) and bool(flat.obs[0, a_in].any())
+    tile = LAY["Tile"]
+    for a in (a_out, a_in):
+        flat.obs[0, a, tile.offset:tile.offset + 675] = 7.0
+    flat.obs_invalidate_sections(abi.OBS_SEC_TILE)
+    flat.observe()
+    rez.observe()
+    _same(flat.obs, rez.obs.clone(), f"P={P} N={NPC}: tracked vs rezero after the Tile invalidate")
+    orc = sc.make_oracle(sc.config(P, NPC))
+    orc.set_state(shrunk)
+    _same(flat.obs, _oracle_rows(orc, flat.device), f"P={P} N={NPC}: tracked vs oracle after the Tile invalidate")
+    assert flat.get_fault() == 0 and rez.get_fault() == 0
     flat.close()
     rez.close()

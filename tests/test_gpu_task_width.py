@@ -4,8 +4,9 @@ length, every other offset is a compile-time constant (csrc/obs_layout.h). 64 is
 floats the full-write kernel prefetches per row, 2,112 above (its tail loop runs).
 
   P = 24, NPC = 40 (S = 64): the tracked handle runs flat_obs_kernel<., 0>, the NMMO_OBS_REZERO=1
-    handle obs_kernel<., true>;
-  P = 13, NPC = 6 (S = 19, not a multiple of 8): the tracked handle runs obs_kernel<., false>;
+    handle the full-write obs_kernel;
+  P = 13, NPC = 6 (S = 19, not a multiple of 8): the tracked handle runs flat_obs_kernel<., 0, false>
+    (the Entity columns staged element by element);
   at 2,112: a wire buffer decoded on store (wire_expand_kernel) and a record-stored batch decoded on
     gather (record_gather_kernel) against the flat rows of the same state."""
 
