@@ -224,16 +224,22 @@ __device__ __forceinline__ int ao_clamp_pos(int x) { return min(max(x, kVision),
 struct AoNoop {
   __device__ void operator()() const {}
 };
-template <int kAgents = kAoAgents, int kRowDw = kAoWinRowBytes / 4, typename F = AoNoop, typename B = AoNoop>
-__device__ inline void ao_stage_windows(const ObsParams& p, int e, int g, const int16_t* T, int Sp, uint32_t* ws, uint2* is,
-                                        F before_barrier = F(), B before_writes = B()) {
+// ao_stage_windows_at: the window thread's agent's position (pr, pc: any value in the other threads)
+// passed in, for a kernel that holds no staged columns (the flat rows' mirror variant).
+// kAlways: every thread loads (pr, pc a position in the map in every thread; the item word from a
+// clamped index), so no load sits under a branch: a conditional load is waited on at its branch's
+// join, which put the loads a caller has in flight and these in two memory round trips.
+template <int kAgents = kAoAgents, int kRowDw = kAoWinRowBytes / 4, bool kAlways = false, typename F = AoNoop,
+          typename B = AoNoop>
+__device__ __forceinline__ void ao_stage_windows_at(const ObsParams& p, int e, int g, int pr, int pc, uint32_t* ws, uint2* is,
+                                           F before_barrier = F(), B before_writes = B()) {
   static_assert(kRowDw == 4 || kRowDw == 5, "window row: 5 aligned dwords, or 4 realigned");
   const int tid = threadIdx.x, P = p.P;
   const int la = tid / 15, row = tid - 15 * la, a = g * kAgents + la;
   const bool win = tid < kAgents * 15 && a < P;
   uint32_t d[5] = {0u, 0u, 0u, 0u, 0u};
-  if (win) {
-    const int r = ao_clamp_pos(T[F_ROW * Sp + a]), c = ao_clamp_pos(T[F_COL * Sp + a]);
+  if (kAlways || win) {
+    const int r = ao_clamp_pos(pr), c = ao_clamp_pos(pc);
     const int base = (r - kVision + row) * kSize + c - kVision;
     const uint32_t* src = reinterpret_cast<const uint32_t*>(p.mat + (size_t)e * kTiles) + (base >> 2);
 #pragma unroll
@@ -245,15 +251,24 @@ __device__ inline void ao_stage_windows(const ObsParams& p, int e, int g, const 
   }
   uint2 iw = make_uint2(0u, 0u);
   const bool itm = tid < kAgents * kInv && g * kAgents + tid / kInv < P;
-  if (itm) iw = p.items[((size_t)e * P + g * kAgents) * kInv + tid];
+  if constexpr (kAlways) iw = p.items[(size_t)e * P * kInv + min(g * kAgents * kInv + tid, P * kInv - 1)];
+  else if (itm) iw = p.items[((size_t)e * P + g * kAgents) * kInv + tid];
   before_writes();
   if (win) {
 #pragma unroll
     for (int k = 0; k < kRowDw; k++) ws[tid * kRowDw + k] = d[k];  // tid = la * 15 + row
   }
-  if (tid < kAgents * kInv) is[tid] = iw;
+  if (tid < kAgents * kInv) is[tid] = kAlways && !itm ? make_uint2(0u, 0u) : iw;
   before_barrier();
   __syncthreads();
+}
+template <int kAgents = kAoAgents, int kRowDw = kAoWinRowBytes / 4, typename F = AoNoop, typename B = AoNoop>
+__device__ inline void ao_stage_windows(const ObsParams& p, int e, int g, const int16_t* T, int Sp, uint32_t* ws, uint2* is,
+                                        F before_barrier = F(), B before_writes = B()) {
+  const int tid = threadIdx.x, a = g * kAgents + tid / 15;
+  const bool win = tid < kAgents * 15 && a < p.P;
+  ao_stage_windows_at<kAgents, kRowDw, false>(p, e, g, win ? T[F_ROW * Sp + a] : 0, win ? T[F_COL * Sp + a] : 0, ws, is,
+                                       before_barrier, before_writes);
 }
 // Per-lane byte offsets of window tiles t = lane + 64 i (i < 4) in an agent's staged rows
 // (row(t) * kRowBytes + col(t)), two 16-bit values per register

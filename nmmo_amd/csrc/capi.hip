@@ -54,6 +54,10 @@ struct NmmoHandle {
   uint64_t* d_zext = nullptr;  // flat rows' extended state (ObsParams::zext)
   bool zskip = true;
   bool wire_fuse = true;  // the tick writes the wire count words (DevState::wf); NMMO_WIRE_FUSE=0 at create: off
+  // flat rows, 384 slots / 128 players, every system: a step's tick writes the entity mirror its own
+  // obs launch reads (DevState::fm; pk in d_wpk); NMMO_FLAT_FUSE=0 at create: off
+  int16_t* d_frows = nullptr;
+  bool flat_fuse = true;
   const void* zbuf = nullptr;  // the bound obs buffer (nmmo_obs_bind) and its tag
   uint64_t ztag = 0;
   unsigned long long* d_rows_out = nullptr;  // nmmo_set_obs_counter
@@ -175,7 +179,8 @@ void nmmo_destroy(NmmoHandle* h) {
   void* bufs[] = {h->d_env,  h->d_ent,   h->d_ring,  h->d_mat,   h->d_dep,   h->d_bank,
                   h->d_task, h->d_seeds, h->d_items, h->d_iring, h->d_mlist, h->d_mcount,
                   h->d_events, h->d_tasks, h->d_assign, h->d_tstate, h->d_ws, h->d_uniq, h->d_wenv, h->d_wdrop, h->d_task_cum,
-                  h->d_wcount, h->d_wmcount, h->d_wrank, h->d_wpk, h->d_foreign, h->d_zrow, h->d_zext};  // d_zst lives in d_zrow's allocation
+                  h->d_wcount, h->d_wmcount, h->d_wrank, h->d_wpk, h->d_foreign, h->d_zrow, h->d_zext,
+                  h->d_frows};  // d_zst lives in d_zrow's allocation
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   delete h;
@@ -241,6 +246,12 @@ int nmmo_create(const NmmoConfig* cfg, int32_t n_envs, uint64_t seed, int32_t de
     h->zskip = !(rz && rz[0] == '1');
     const char* wf = getenv("NMMO_WIRE_FUSE");  // A/B: the count kernel instead of the tick-fused count
     h->wire_fuse = !(wf && wf[0] == '0');
+    const char* ff = getenv("NMMO_FLAT_FUSE");  // A/B: the obs kernel stages the Entity columns itself
+    h->flat_fuse = !(ff && ff[0] == '0');
+  }
+  if (cfg->obs_layout == NMMO_OBS_FLAT && h->flat_fuse && cfg->systems == NMMO_SYS_ALL && S == 384 && P == 128) {
+    ALLOC(h->d_wpk, n * (size_t)kMaxSlots * 4);
+    ALLOC(h->d_frows, n * (size_t)S * kMirrorCols * 2);
   }
   if (cfg->obs_layout == NMMO_OBS_WIRE) {
     ALLOC(h->d_wrank, n * (size_t)kMaxSlots * 2);
@@ -299,6 +310,8 @@ static ObsParams obs_params(NmmoHandle* h, void* obs) {
   p.zext = h->d_zext;
   p.ztag = h->d_zrow && h->zskip && obs && obs == h->zbuf ? h->ztag : 0;
   p.rows_out = h->d_rows_out;
+  p.fpk = nullptr;  // (a step's own tick writes the mirror: step_impl sets them)
+  p.frows = nullptr;
   p.counted = 0;
   p.recs = nullptr;  // (a step's outputs: step_impl sets them)
   p.fault_dst = nullptr;
@@ -386,6 +399,19 @@ static int step_impl(NmmoHandle* h, const int32_t* env_ids, int32_t n_ids, const
     st.wf.n_envs = st.n_envs;
     st.wf.spawn_immunity = h->cfg.spawn_immunity;
   }
+  // a step whose obs launch goes to flat_obs_kernel (the bound, tracked buffer) at the specialised
+  // shape: the tick writes the entity mirror that launch reads instead of staging the env's Entity
+  // columns (tick.hip flat_mirror_fused). The mirror is trusted by this call's obs launch alone --
+  // over an env list too, which the tick and the obs launch share -- so nothing else (reset,
+  // nmmo_observe, nmmo_set_state, ...) has to keep it coherent. The wrapper launch between the two
+  // reads the entity table and writes only its own state.
+  const bool mirror = do_obs && h->d_frows && h->cfg.obs_layout == NMMO_OBS_FLAT && obs_params(h, obs).ztag != 0 &&
+                      st.cfg.systems == NMMO_SYS_ALL && st.S == 384 && st.P == 128;
+  if (mirror) {
+    st.fm.pk = h->d_wpk;
+    st.fm.rows = h->d_frows;
+    st.fm.spawn_immunity = h->cfg.spawn_immunity;
+  }
   if (rec) HIP_TRY(hipEventRecord(ev[0], s));
   HIP_TRY(launch_tick(st, actions, nullptr, rew, term, trunc, mask, 0, s));
   if (rec) HIP_TRY(hipEventRecord(ev[1], s));
@@ -401,6 +427,10 @@ static int step_impl(NmmoHandle* h, const int32_t* env_ids, int32_t n_ids, const
     op.env_list = env_ids;
     op.n_list = n_ids;
     op.counted = st.wf.wire != nullptr;
+    if (mirror) {
+      op.fpk = h->d_wpk;
+      op.frows = h->d_frows;
+    }
     if (op.wire && h->d_recs) {
       op.recs = h->d_recs;
       op.fault_dst = h->d_recs_fault;

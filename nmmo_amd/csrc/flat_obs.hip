@@ -104,6 +104,24 @@ static_assert(kAoAgents != 16 ||
                    5 * ((fo_lds_bytes(kMaxSlots) + kFoLdsGranule - 1) / kFoLdsGranule * kFoLdsGranule) <= 160 * 1024),
               "5 workgroups per CU");
 
+// The mirror variant (kMirror: the obs launch of a step whose tick wrote DevState::fm, 384 slots): no
+// staged columns and no pk. LDS: the workgroup's own agents' mirror rows [16][32] int16 | the first
+// kFoGather visible entities' mirror rows of every agent [16][kFoGather][32] int16 | the listings'
+// pool | every agent's visible rows [16][kFoVisw] | the window rows | the item words (a region of
+// their own: nothing is aliased, so the windows need no barrier ahead of their writes).
+// kFoGather: the smallest even count covering >= 99 % of the agent rows of the bench scenario
+// (tools/flat_window_counts.py, DESIGN §3.2d: 99.7 % see at most 12 entities, 99.3 % at most 11);
+// the rows past it take a global load each, in a loop of their own. A multiple of 4: a 16-B load
+// instruction of a wave gathers 16 rows (4 lanes per 64-B row).
+constexpr int kFoGather = 12;
+static_assert(kFoGather % 4 == 0 && kFoGather <= 16 && kFoGather <= kNObs, "gathered rows");
+constexpr size_t kFoOwnBytes = (size_t)kAoAgents * kMirrorCols * 2;
+constexpr size_t kFoGatBytes = (size_t)kAoAgents * kFoGather * kMirrorCols * 2;
+constexpr size_t kFoMirrorLds =
+    kFoOwnBytes + kFoGatBytes + (size_t)kFoListPool + (size_t)kAoAgents * kFoVisw * 4 + kFoWinBytes + kFoItemBytes;
+static_assert(5 * ((kFoMirrorLds + kFoLdsGranule - 1) / kFoLdsGranule * kFoLdsGranule) <= 160 * 1024 &&
+                  kFoOwnBytes % 16 == 0 && kFoGatBytes % 16 == 0, "5 workgroups per CU");
+
 // Low 64 bits of the 128-bit field (hi:lo) shifted left by kSh (right when negative): the part of a
 // section whose bit 0 sits at chunk bit kSh.
 template <int kSh>
@@ -263,18 +281,25 @@ typedef const __attribute__((address_space(4))) ObsParams* FoArgs;  // the kerne
 // it the staged-column offsets are immediates instead of uniform values the agent loop keeps live.
 // 5 waves per SIMD (5 workgroups of 4 waves per CU): 96 VGPRs, which the kernel fits without scratch.
 // kAligned: S % 8 == 0 (agent_obs.h's 16-B column loads); false stages any S element by element.
-template <bool kWrap, int kS, bool kAligned = true>
+// kMirror: p.fpk / p.frows hold the tick's entity mirror of this very state (kernels.h): the packed
+// row words come from p.fpk, the workgroup's own agents' rows and its agents' first kFoGather
+// visible rows from p.frows, and nothing is staged (kFoGather above).
+template <bool kWrap, int kS, bool kAligned = true, bool kMirror = false>
 __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per_eu(5, 5))) flat_obs_kernel(ObsParams p) {
+  static_assert(!kMirror || (kS == kMaxSlots && kAligned), "the mirror variant: 384 slots");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int S = kS ? kS : p.S, P = p.P, Sp = ao_stride(S), tdim = p.task_dim, elems = kFlatTask + tdim + kTileN;
-  int16_t* T = reinterpret_cast<int16_t*>(smem);
-  uint16_t* mpo = reinterpret_cast<uint16_t*>(smem + ao_columns_lds(S));       // [1024] price | owner << 8
-  uint32_t* visw_all = reinterpret_cast<uint32_t*>(mpo) + kFoListPool / 4;       // [4][100]
+  constexpr int kPerWave = kAoAgents / kAoWaves;
+  static_assert(!kMirror || (kPerWave * kFoGather) % 16 == 0, "gather: 16 rows per load instruction");
+  int16_t* T = reinterpret_cast<int16_t*>(smem);  // kMirror: own, the workgroup's own agents' mirror rows
+  int16_t* gat = reinterpret_cast<int16_t*>(smem + kFoOwnBytes);               // kMirror: the gathered rows
+  uint16_t* mpo = reinterpret_cast<uint16_t*>(smem + (kMirror ? kFoOwnBytes + kFoGatBytes : ao_columns_lds(S)));  // [1024] price | owner << 8
+  uint32_t* visw_all = reinterpret_cast<uint32_t*>(mpo) + kFoListPool / 4;       // [4][100] (kMirror: [16][100])
   uint2* mtop = reinterpret_cast<uint2*>(visw_all) - 1;  // mtop[-k]: listing k's item word (k < fo_staged(nm))
-  uint32_t* wst = visw_all + kAoWaves * kFoVisw;                               // [16][15][4] window rows
+  uint32_t* wst = visw_all + (kMirror ? kAoAgents : kAoWaves) * kFoVisw;        // [16][15][4] window rows
   uint32_t* pk = wst;  // the packed datastore rows, until the window rows are written (fo_lds_bytes)
-  uint2* ist = reinterpret_cast<uint2*>(fo_items_in_T(S) ? smem + (size_t)F_ROW * Sp * 2   // [16][12] item words
-                                                         : reinterpret_cast<unsigned char*>(wst) + kFoWinBytes);
+  uint2* ist = reinterpret_cast<uint2*>(!kMirror && fo_items_in_T(S) ? smem + (size_t)F_ROW * Sp * 2   // [16][12] item words
+                                                                     : reinterpret_cast<unsigned char*>(wst) + kFoWinBytes);
 #if NMMO_FO_XCD  // 1-D grid, an env's groups back to back on one XCD (agent_obs.h ao_env_group)
   int el, g;
   ao_env_group(p.env_list ? p.n_list : p.n_envs, (p.P + kAoAgents - 1) / kAoAgents, el, g);
@@ -293,10 +318,28 @@ __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per
   // words and this wave's agents' words; (2) after the stage's LDS writes, the listed items, the
   // agents' extended row state and the workgroup's windows. (Issued where each was first needed,
   // the count -> mlist -> item chain, the stage, the windows and the extended state were six.)
+  // (kMirror: trip 1 loads the packed row words, the own agents' mirror rows and the positions
+  // instead of the stage's columns, and the windows of trip 2 follow the compaction, which runs for
+  // all of the wave's agents between the trips; trip 2 also gathers their visible rows)
   AoStage sg;
-  ao_stage_load<kAligned>(p, e, sg);
+  const int16_t* M = kMirror ? p.frows + (size_t)e * S * kMirrorCols : nullptr;  // the env's mirror rows
+  uint32_t pr[kAoRows];  // this lane's datastore rows 1 + lane + 64 i
+  uint4 ow = make_uint4(0u, 0u, 0u, 0u);
+  int wpr = 0, wpc = 0;  // kMirror: the window thread's agent's position
+  if constexpr (kMirror) {
+    sg.nm = p.mcount[e];
+    sg.mv = p.mlist[(size_t)e * NMMO_MARKET_ROWS + min(tid, NMMO_MARKET_ROWS - 1)];
+#pragma unroll
+    for (int i = 0; i < kAoRows; i++) pr[i] = p.fpk[(size_t)e * kMaxSlots + lane + 64 * i];
+    // (every wave loads the 1 KB, wave 0 writes it: no branch around a load)
+    ow = reinterpret_cast<const uint4*>(M + (size_t)min(g * kAoAgents + ((tid >> 2) & (kAoAgents - 1)), P - 1) * kMirrorCols)[tid & 3];
+    const int16_t* wr = M + (size_t)min(g * kAoAgents + tid / 15, P - 1) * kMirrorCols;
+    wpr = wr[F_ROW];
+    wpc = wr[F_COL];
+  } else {
+    ao_stage_load<kAligned>(p, e, sg);
+  }
   const int16_t* E = p.ent + (size_t)e * NMMO_NF * S;
-  constexpr int kPerWave = kAoAgents / kAoWaves;
   const int abase = g * kAoAgents + w;
   int my_task = 0, my_prev = -1, my_alive = 0;  // lane j: agent abase + 4 j
   uint64_t my_z = 0, my_s = 0;                  // its row state tag and word
@@ -305,7 +348,7 @@ __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per
     const int aj = min(abase + kAoWaves * min(lane, kPerWave - 1), P - 1);
     const size_t ai = (size_t)e * P + aj;
     my_task = p.assign[ai];
-    my_alive = E[F_ALIVE * S + aj];
+    my_alive = kMirror ? M[(size_t)aj * kMirrorCols + kMirrorCols - 1] : E[F_ALIVE * S + aj];
     if (p.zrow) {
       my_z = p.zrow[ai];
       my_s = p.zst[ai];
@@ -313,13 +356,19 @@ __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per
     if constexpr (kWrap)
       if (p.ws) my_prev = p.ws[ai].prev_price;
   }
-  ao_stage_store<kAligned>(p, e, T, pk, sg);
+  uint32_t my_rc;  // its position, row | col << 16 (T's row / column columns are reused below)
+  if constexpr (kMirror) {
+    const int16_t* mr = M + (size_t)min(abase + kAoWaves * min(lane, kPerWave - 1), P - 1) * kMirrorCols;
+    my_rc = (uint32_t)(uint16_t)mr[F_ROW] | (uint32_t)(uint16_t)mr[F_COL] << 16;
+    if (tid < kAoAgents * 4) reinterpret_cast<uint4*>(T)[tid] = ow;  // own[la][32], la = tid / 4
+  } else {
+    ao_stage_store<kAligned>(p, e, T, pk, sg);
+  }
   if (!mine) {
     my_task = 0, my_prev = -1, my_alive = 0;
     my_z = my_s = 0;
   }
-  uint32_t my_rc;  // its position, row | col << 16 (T's row / column columns are reused below)
-  {
+  if constexpr (!kMirror) {
     const int aj = min(abase + kAoWaves * min(lane, kPerWave - 1), P - 1);
     my_rc = (uint32_t)(uint16_t)T[F_ROW * Sp + aj] | (uint32_t)(uint16_t)T[F_COL * Sp + aj] << 16;
   }
@@ -327,10 +376,44 @@ __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per
   wst_[1] = __builtin_amdgcn_s_memtime();
 #endif
 
-  uint32_t pr[kAoRows];  // this lane's datastore rows 1 + lane + 64 i
+  if constexpr (!kMirror) {
 #pragma unroll
-  for (int i = 0; i < kAoRows; i++) pr[i] = pk[lane + 64 * i];
-  uint32_t* visw = visw_all + w * kFoVisw;
+    for (int i = 0; i < kAoRows; i++) pr[i] = pk[lane + 64 * i];
+  }
+  uint32_t* visw = visw_all + w * (kMirror ? kPerWave : 1) * kFoVisw;  // kMirror: agent j's at visw + j * kFoVisw
+  // kMirror: the window compaction of all of the wave's agents in the realm, from pr[] (dead after
+  // it), then the loads of their first kFoGather visible rows: 4 lanes per 64-B row, row t =
+  // lane / 4 + 16 i of the wave's kPerWave * kFoGather (agent t / kFoGather's visible row
+  // t % kFoGather; a row past its count loads the env's slot 0 and is never read)
+  int my_nv = 0;  // lane j: agent j's visible count (capped at kNObs)
+  constexpr int kGatIt = kPerWave * kFoGather / 16;
+  static_assert(kGatIt >= 1 && kGatIt <= 4, "gather loads");
+  uint4 gq0, gq1, gq2, gq3;  // (no array: one indexed from the listings' lambda went to scratch)
+  gq0 = gq1 = gq2 = gq3 = make_uint4(0u, 0u, 0u, 0u);
+  if constexpr (kMirror) {
+#pragma unroll
+    for (int j = 0; j < kPerWave; j++) {
+      int nvj = 0;
+      if (__builtin_amdgcn_readlane(my_alive, j) && !(NMMO_FO_ABL & 32)) {
+        const int rcj = __builtin_amdgcn_readlane((int)my_rc, j);
+        nvj = min(fo_compact(pr, (int16_t)(rcj & 0xFFFF), rcj >> 16, visw + j * kFoVisw), kNObs);
+      }
+      if (lane == j) my_nv = nvj;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    auto gather = [&](int i) {
+      const int t = (lane >> 2) + 16 * i, tj = t / kFoGather, tk = t - tj * kFoGather;
+      const uint32_t vw = visw[tj * kFoVisw + tk];
+      const int slot = tk < __shfl(my_nv, tj) ? ao_slot(vw) : 0;
+      return reinterpret_cast<const uint4*>(M + (size_t)min(slot, S - 1) * kMirrorCols)[lane & 3];
+    };
+    gq0 = gather(0);
+    if constexpr (kGatIt > 1) gq1 = gather(1);
+    if constexpr (kGatIt > 2) gq2 = gather(2);
+    if constexpr (kGatIt > 3) gq3 = gather(3);
+  }
   const uint8_t* wsb = reinterpret_cast<const uint8_t*>(wst);
   const float tickf = (float)p.env[(size_t)e * NMMO_NE + E_TICK];
   const bool exch = (p.systems & NMMO_SYS_ITEM) && (p.systems & NMMO_SYS_EXCHANGE);
@@ -351,7 +434,7 @@ __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per
   const int ja = lane < 40 ? lane / 10 : lane - 40, ji = lane / 12;
   const bool img_ok = lane < 44 && abase + kAoWaves * ja < P && ((zextv >> ja) & 1);
   const bool pinv_ok = lane < 48 && abase + kAoWaves * ji < P && ((zextv >> ji) & 1);
-  if (p.zext) {
+  if (kMirror || p.zext) {  // (kMirror: never NULL, launch_flat_obs; no branch around trip 2's loads)
     const int aa = min(abase + kAoWaves * min(ja, kPerWave - 1), P - 1);
     const int ai = min(abase + kAoWaves * min(ji, kPerWave - 1), P - 1);
     img = reinterpret_cast<const uint2*>(p.zext)[((size_t)e * P + aa) * kZext + (lane < 40 ? lane % 10 : 10)];
@@ -362,7 +445,14 @@ __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per
   // the listings (ascending row) into LDS ahead of the windows' barrier, which publishes them.
   // The window rows overwrite pk, and at S = 384 the item words overwrite T's row / column columns:
   // a barrier after every wave's pr / my_rc loads and the windows' own position reads, ahead of those writes
-  ao_stage_windows<kAoAgents, kFoWinRowBytes / 4>(p, e, g, T, Sp, wst, ist, [&]() {
+  auto listings = [&]() {
+    if constexpr (kMirror) {  // the gathered rows [w * kPerWave + j][k][32] beside the listings
+      uint4* gd = reinterpret_cast<uint4*>(gat) + w * kGatIt * 64 + lane;
+      gd[0] = gq0;
+      if constexpr (kGatIt > 1) gd[64] = gq1;
+      if constexpr (kGatIt > 2) gd[128] = gq2;
+      if constexpr (kGatIt > 3) gd[192] = gq3;
+    }
     if (tid < nm) {
       mpo[tid] = (uint16_t)(it_price(lwd) | ((sg.mv >> 16) & 255) << 8);
       if (tid < nst) mtop[-tid] = lwd;
@@ -374,7 +464,11 @@ __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per
       mpo[j] = (uint16_t)(it_price(wd) | own << 8);
       if (j < nst) mtop[-j] = wd;
     }
-  }, []() { __syncthreads(); });
+  };
+  if constexpr (kMirror)  // (no region is aliased: no barrier ahead of the writes)
+    ao_stage_windows_at<kAoAgents, kFoWinRowBytes / 4, true>(p, e, g, wpr, wpc, wst, ist, listings);
+  else
+    ao_stage_windows<kAoAgents, kFoWinRowBytes / 4>(p, e, g, T, Sp, wst, ist, listings, []() { __syncthreads(); });
 #if NMMO_FO_STAMPS
   wst_[2] = __builtin_amdgcn_s_memtime();
 #endif
@@ -454,8 +548,12 @@ __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per
     const int la = a - g * kAoAgents;
     const int rcj = __builtin_amdgcn_readlane((int)my_rc, j);
     const int r = (int16_t)(rcj & 0xFFFF), c = rcj >> 16;
-    const int gold = __builtin_amdgcn_readfirstlane(T[F_GOLD * Sp + a]);
-    const int aid = __builtin_amdgcn_readfirstlane(T[F_ID * Sp + a]);
+    // the agent's own columns: T[f * Spa + tia] (kMirror: its row of the own tile, fields adjacent)
+    const int16_t* Ta = kMirror ? T + la * kMirrorCols : T;
+    const int Spa = kMirror ? 1 : Sp, tia = kMirror ? 0 : a;
+    if constexpr (kMirror) visw = visw_all + (w * kPerWave + j) * kFoVisw;
+    const int gold = __builtin_amdgcn_readfirstlane(Ta[F_GOLD * Spa + tia]);
+    const int aid = __builtin_amdgcn_readfirstlane(Ta[F_ID * Spa + tia]);
     const uint8_t* wa = wsb + la * kFoWinAgentBytes;  // (rows realigned while staging: no column term)
     uint32_t wm[4];
 #pragma unroll
@@ -463,10 +561,15 @@ __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per
     const uint2 it = lane < kInv ? ist[la * kInv + lane] : make_uint2(0u, 0u);
     const uint32_t mv = ao_move_bits(wm[1]);
     const int ninv = __builtin_ctzll(~__ballot(lane < kInv && it_type(it) != 0));  // occupied prefix
-    const int nv = (NMMO_FO_ABL & 32) ? 0 : min(fo_compact(pr, r, c, visw), kNObs);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    int nv;
+    if constexpr (kMirror) {  // compacted in the prologue
+      nv = __builtin_amdgcn_readlane(my_nv, j);
+    } else {
+      nv = (NMMO_FO_ABL & 32) ? 0 : min(fo_compact(pr, r, c, visw), kNObs);
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
 
     FO_STAMP(1);
     const bool ext = (zextv >> j) & 1;  // the row's extended state is valid
@@ -475,7 +578,7 @@ __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per
     if (!(NMMO_FO_ABL & 1)) {
       AoAgent ag;
       ag.a = a;
-      ag.ti = a;
+      ag.ti = tia;
       ag.r = r;
       ag.c = c;
       ag.gold = gold;
@@ -484,7 +587,7 @@ __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per
       ag.ninv = ninv;
       ag.prev_price = kWrap ? __builtin_amdgcn_readlane(my_prev, j) : -1;
       ag.mv = mv;
-      const AoSections x = ao_sections<kWrap>(p, T, Sp, visw, ag, it);
+      const AoSections x = ao_sections<kWrap>(p, Ta, Spa, visw, ag, it);
       FO_STAMP(2);
       fg.ext = ext;
       fo_put<0>(row, fg, fo_chunk<0>(x), 0.f, 0.f);
@@ -527,17 +630,40 @@ __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per
       // the row / column lanes take the packed word's fields (their columns of T hold the item words)
       const bool epos = (lane & 31) == F_ROW || (lane & 31) == F_COL;
       const uint32_t esh = (lane & 31) == F_COL ? 16u : 0u;
+      // kMirror: the first kFoGather rows from the gathered tile (lane = field: 128 contiguous bytes
+      // per pass); the rows past them from the mirror in HBM, in a loop of their own (as the
+      // listings past the staged ones below: the common path issues no global load)
+      const int16_t* gj = gat + (size_t)(w * kPerWave + j) * kFoGather * kMirrorCols;
+      const int nst2 = kMirror ? min(nv2, kFoGather) : nv2;
 #pragma unroll 1
-      for (int k0 = 0; k0 < nv2; k0 += 2) {
+      for (int k0 = 0; k0 < nst2; k0 += 2) {
         const int k = k0 + eh;
         if (ef < NMMO_N_ENTITY_COLS) {
           float v = 0.f;
           if (k < nv) {
             const uint32_t vw = visw[k];
-            const int tv = T[ef * Sp + ao_slot(vw)];
+            const int tv = kMirror ? gj[k * kMirrorCols + ef] : T[ef * Sp + ao_slot(vw)];
             v = (float)(epos ? (int)((vw >> esh) & 255u) : tv);
           }
           fo_st(row, de + k0 * NMMO_N_ENTITY_COLS, v);
+        }
+      }
+      if constexpr (kMirror) {
+        if (nv2 > kFoGather) {
+          const int16_t* Mk = kp->frows + (size_t)e * kMaxSlots * kMirrorCols;
+#pragma unroll 1
+          for (int k0 = kFoGather; k0 < nv2; k0 += 2) {
+            const int k = k0 + eh;
+            if (ef < NMMO_N_ENTITY_COLS) {
+              float v = 0.f;
+              if (k < nv) {
+                const uint32_t vw = visw[k];
+                const int tv = Mk[(size_t)min(ao_slot(vw), kMaxSlots - 1) * kMirrorCols + ef];
+                v = (float)(epos ? (int)((vw >> esh) & 255u) : tv);
+              }
+              fo_st(row, de + k0 * NMMO_N_ENTITY_COLS, v);
+            }
+          }
         }
       }
       const int hz = max(nv2, hv);
@@ -640,9 +766,11 @@ __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per
     if (lane == 0 && (size_t)e * P + a < (1u << 17))
       for (int k = 0; k < kFoStamps; k++) fo_stamp_buf[(size_t)e * P + a][k] = fst[k];
 #endif
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the next agent reuses visw
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if constexpr (!kMirror) {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the next agent reuses visw
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
   }
 #if NMMO_FO_STAMPS
   wst_[4] = __builtin_amdgcn_s_memtime();
@@ -669,7 +797,11 @@ hipError_t launch_flat_obs(const ObsParams& p, hipStream_t stream) {
   const dim3 grid(ne, (p.P + kAoAgents - 1) / kAoAgents), block(64 * kAoWaves);
 #endif
   const size_t lds = fo_lds_bytes(p.S);
-  if (p.S == kMaxSlots) {
+  if (p.frows) {  // the tick's entity mirror of this state (step_impl: 384 slots only)
+    if (!p.fpk || !p.zext || p.S != kMaxSlots) return hipErrorInvalidValue;
+    if (p.wflags) hipLaunchKernelGGL((flat_obs_kernel<true, kMaxSlots, true, true>), grid, block, kFoMirrorLds, stream, p);
+    else hipLaunchKernelGGL((flat_obs_kernel<false, kMaxSlots, true, true>), grid, block, kFoMirrorLds, stream, p);
+  } else if (p.S == kMaxSlots) {
     if (p.wflags) hipLaunchKernelGGL((flat_obs_kernel<true, kMaxSlots>), grid, block, lds, stream, p);
     else hipLaunchKernelGGL((flat_obs_kernel<false, kMaxSlots>), grid, block, lds, stream, p);
   } else if (p.S % 8 != 0) {

@@ -66,7 +66,18 @@ struct DevState {
     int n_envs;
     int spawn_immunity;
   } wf;
+  // The flat rows' entity mirror written by the tick (tick.hip flat_mirror_fused, the same
+  // specialisation): set by a step whose own obs launch goes to flat_obs_kernel, which then reads
+  // these instead of staging the env's Entity columns; rows == NULL = off. Valid only for the obs
+  // launch of the step that wrote them.
+  struct FlatMirror {
+    uint32_t* pk;    // [n][kMaxSlots] packed datastore-row words (ObsParams::fpk)
+    int16_t* rows;   // [n][S][kMirrorCols] slot-major copy of the obs Entity columns (ObsParams::frows)
+    int spawn_immunity;
+  } fm;
 };
+constexpr int kMirrorCols = 32;  // int16 per mirror row: the 31 obs Entity columns | alive (64 B)
+static_assert(NMMO_N_ENTITY_COLS < kMirrorCols, "mirror row");
 // grid size and env of workgroup b of a launch over an env list (NULL = all n envs)
 __host__ __device__ inline int list_grid(const int32_t* list, int n_list, int n) { return list ? n_list : n; }
 
@@ -124,6 +135,10 @@ struct ObsParams {
   const uint8_t* trunc;
   const uint8_t* mask;
   unsigned long long* rows_out;  // optional [n][2]: += rows this launch wrote, bytes it stored, per env
+  // flat rows, the obs launch of a step whose tick wrote the entity mirror (DevState::fm); NULL =
+  // the kernel stages the Entity columns from `ent` itself
+  const uint32_t* fpk;   // [n][kMaxSlots]
+  const int16_t* frows;  // [n][S][kMirrorCols]
 };
 constexpr uint64_t kZsZero = 1ull << 20;
 constexpr uint64_t kZsExt = 1ull << 21;  // the row's extended state (ObsParams::zext) is valid

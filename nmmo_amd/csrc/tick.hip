@@ -2441,6 +2441,29 @@ __device__ __forceinline__ void tick_env(Ctx& c, Heads hd, bool defer, DepQ dq, 
   }
 }
 
+// A slot's fields the end-of-tick epilogues (wire_count_fused, flat_mirror_fused) pack, read from the
+// staged table by the slot's thread before the barrier that frees the epilogues' scratch
+struct SlotPack {
+  bool in;
+  int ds, r, col, id, ta, npc;
+};
+template <int kS>
+__device__ __forceinline__ SlotPack slot_pack_read(const Ctx& c, int s) {
+  SlotPack v;
+  v.in = s < kS && TF(F_ALIVE, s);
+  v.ds = s < kS ? TF(F_DS_ROW, s) : 0, v.r = s < kS ? TF(F_ROW, s) : 0, v.col = s < kS ? TF(F_COL, s) : 0;
+  v.id = s < kS ? TF(F_ID, s) : 0, v.ta = s < kS ? TF(F_TIME_ALIVE, s) : 0, v.npc = s < kS ? TF(F_NPC_TYPE, s) : 0;
+  return v;
+}
+// pk[datastore row - 1] = slot s's ao_pack word (pk holds kAoEmpty everywhere, published by a barrier)
+template <int kS, int kP>
+__device__ __forceinline__ void slot_pack_put(uint32_t* pk, int s, const SlotPack& v, int spawn_immunity) {
+  if (s < kMaxSlots && v.in && (unsigned)(v.ds - 1) < (unsigned)kS) {
+    const bool player = s < kP;
+    pk[v.ds - 1] = ao_pack(s, v.r, v.col, player && v.ta < spawn_immunity, v.npc > 1, player);
+  }
+}
+
 // The tick-fused wire count (DevState::wf): wire.hip wire_count_kernel's outputs -- per agent in
 // the realm its count word (visible entities, the first kNObs, and its occupied inventory prefix),
 // the env's entity-table ranks and size, its listing count and payload bytes, the packed word of
@@ -2469,9 +2492,9 @@ __device__ __forceinline__ void wire_count_fused(Ctx& c, const DevState& st, int
   }
   // this thread's slot (blockDim >= S), read before the barrier that frees the scratch
   const int s = tid;
-  const bool in = s < S && TF(F_ALIVE, s);
-  const int ds = s < S ? TF(F_DS_ROW, s) : 0, r = s < S ? TF(F_ROW, s) : 0, col = s < S ? TF(F_COL, s) : 0;
-  const int id = s < S ? TF(F_ID, s) : 0, ta = s < S ? TF(F_TIME_ALIVE, s) : 0, npc = s < S ? TF(F_NPC_TYPE, s) : 0;
+  const SlotPack sv = slot_pack_read<kS>(c, s);
+  const bool in = sv.in;
+  const int r = sv.r, col = sv.col, id = sv.id;
   int ninv = 0;
   if (tid < P) {  // the occupied inventory prefix
     const uint2* inv = c.inv + tid * kInv;
@@ -2495,10 +2518,7 @@ __device__ __forceinline__ void wire_count_fused(Ctx& c, const DevState& st, int
   __syncthreads();
   if (s < kMaxSlots) {
     pos[s] = in ? ((uint32_t)(uint16_t)r << 16) | (uint32_t)(uint16_t)col : kOut;
-    if (in && (unsigned)(ds - 1) < (unsigned)S) {
-      const bool player = s < P;
-      pk[ds - 1] = ao_pack(s, r, col, player && ta < st.wf.spawn_immunity, npc > 1, player);
-    }
+    slot_pack_put<kS, kP>(pk, s, sv, st.wf.spawn_immunity);
   }
   __syncthreads();
   const WireView v = wire_view(st.wf.wire, st.wf.n_envs, P);
@@ -2544,6 +2564,44 @@ __device__ __forceinline__ void wire_count_fused(Ctx& c, const DevState& st, int
     v.ecount[e] = (uint16_t)ne;
     v.env_off[e] = wire_table_bytes(ne) + *bytes + 32 * nm;
   }
+}
+
+// The flat rows' entity mirror (DevState::fm): what flat_obs_kernel's workgroups otherwise each
+// rebuild from the env's 31 Entity columns in HBM -- the packed word of every datastore row
+// (wire_count_fused's, into fm.pk) and a slot-major copy of the obs Entity columns (fm.rows: 64 B
+// per slot, the columns in field order, then alive), so a visible entity's row is one line instead
+// of 31 -- written from the staged table after the store. One thread per slot reads its 31 fields
+// (consecutive slots read consecutive LDS addresses per field) and issues four 16-B stores. Scratch:
+// the item ring (free after the store) holds the packed rows.
+template <int kS, int kP>
+__device__ __forceinline__ void flat_mirror_fused(Ctx& c, const DevState& st, int e) {
+  static_assert(kS > 0 && kS <= kMaxSlots && kS % 64 == 0 && kP > 0 && kP <= 128, "a specialised shape");
+  static_assert((size_t)kMaxSlots * 4 <= (((size_t)kInv * kP * 2 + 15) & ~(size_t)15), "the item ring");
+  static_assert(NMMO_N_ENTITY_COLS == 31 && kMirrorCols == 32, "mirror row");
+  const int tid = threadIdx.x, s = tid;
+  const SlotPack sv = slot_pack_read<kS>(c, s);
+  if (s < kS) {  // (whole waves: kS % 64 == 0)
+    uint4* dst = reinterpret_cast<uint4*>(st.fm.rows + ((size_t)e * kS + s) * kMirrorCols);
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      uint32_t d[4];
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const int f = 8 * q + 2 * k;  // fields f | f + 1 << 16; the spare halfword holds alive
+        const uint32_t lo = (uint16_t)TF(f, s);
+        const uint32_t hi = f + 1 < NMMO_N_ENTITY_COLS ? (uint16_t)TF(f + 1, s) : (uint16_t)TF(F_ALIVE, s);
+        d[k] = lo | hi << 16;
+      }
+      dst[q] = make_uint4(d[0], d[1], d[2], d[3]);
+    }
+  }
+  __syncthreads();  // the store's LDS reads are done: the scratch below overwrites what they read
+  uint32_t* pk = reinterpret_cast<uint32_t*>(c.iring);  // datastore row - 1 -> ao_pack word
+  for (int k = tid; k < kMaxSlots; k += blockDim.x) pk[k] = kAoEmpty;
+  __syncthreads();
+  slot_pack_put<kS, kP>(pk, s, sv, st.fm.spawn_immunity);
+  __syncthreads();
+  for (int k = tid; k < kMaxSlots; k += blockDim.x) st.fm.pk[(size_t)e * kMaxSlots + k] = pk[k];
 }
 
 // End-of-tick listings for the obs and policy kernels (Market rows, Buy mask): ascending row.
@@ -2653,8 +2711,10 @@ __device__ __forceinline__ void tick_body(const DevState& st, const int32_t* __r
   NMMO_STAMP(10);
   store_market(c, st, e);
   store_env(c, st, e);
-  if constexpr (kSys == NMMO_SYS_ALL && kS > 0 && kP > 0)
+  if constexpr (kSys == NMMO_SYS_ALL && kS > 0 && kP > 0) {
     if (st.wf.wire) wire_count_fused<kS, kP>(c, st, e);
+    else if (st.fm.rows) flat_mirror_fused<kS, kP>(c, st, e);
+  }
 #ifdef NMMO_STAMPS
   __syncthreads();
 #endif
