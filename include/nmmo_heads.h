@@ -5,7 +5,8 @@
  * head, masked_fill(mask == 0, -1e9) on the head's logits, a Categorical, then sample / log_prob
  * / entropy. nmh_forward does that for all heads of a row in one gfx950 kernel, reading the mask
  * in place from the obs row; nmh_backward is its gradient with respect to the logits. The
- * semantics are frozen in SPEC.md §15.
+ * semantics are frozen in SPEC.md §15. nmh_pointer_forward / nmh_pointer_backward do the same for
+ * heads whose logits are dot products of a query with candidate keys (SPEC.md §18).
  *
  * Conventions (those of nmmo_hip.h): every call returns 0 or a negative NMH_E_* code and never
  * aborts; nmh_last_error() returns a thread-local message. Argument errors are reported without
@@ -59,6 +60,51 @@ NMH_API int nmh_backward(const NmhHeads* hd, int32_t n_rows, const float* logits
                          const void* mask, int64_t mask_stride, int32_t mask_kind, const int32_t* actions,
                          const float* lse, const float* head_entropy, const float* g_logprob,
                          const float* g_entropy, float* g_logits, int64_t g_stride, void* stream);
+
+/* ---- Pointer heads (SPEC.md §18): a head whose logits are dot products of a per-row query with
+ * per-row candidate keys, as the reference's decoders compute them (baseline_policy.py:222-230),
+ * fused with the masked categorical above. The logits are never materialised, and the key rows of
+ * illegal candidates are never read. */
+#define NMH_MAX_SETS 4
+#define NMH_MAX_KEY_DIM 256
+
+/* head_set[k] = -1: head k is dense, its dims[k] logits are given. head_set[k] = s in
+ * [0, n_sets): head k points into key set s, which has set_rows[s] >= 1 candidates per row, and
+ * dims[k] == set_rows[s] + 1: the last entry is the no-op, whose logit is exactly 0 (the
+ * reference's zero padding row). 0 <= n_sets <= NMH_MAX_SETS and every set is used by a head.
+ * key_dim (D) is a multiple of 4 in 4..NMH_MAX_KEY_DIM; it is not looked at when n_sets == 0.
+ * sum(dims) <= NMH_MAX_DIM. */
+typedef struct NmhPointer {
+  int32_t n_sets;
+  int32_t key_dim;
+  int32_t set_rows[NMH_MAX_SETS];
+  int32_t head_set[NMH_MAX_HEADS];
+} NmhPointer;
+
+/* queries [n_rows, P, D]: one query per pointer head, P = the number of pointer heads, in head
+ * order (NULL iff P == 0). keys: a HOST array of n_sets device pointers, keys[s] [n_rows,
+ * set_rows[s], D] (NULL iff n_sets == 0). Queries and keys are contiguous and 16-byte aligned.
+ * dense [n_rows, dense_stride]: the dense heads' logits concatenated in head order, dense_stride
+ * >= their total (NULL iff no head is dense). mask rows cover all heads as in nmh_forward.
+ * The remaining arguments and every output are those of nmh_forward. */
+NMH_API int nmh_pointer_forward(const NmhHeads* hd, const NmhPointer* pt, int32_t n_rows, const float* queries,
+                                const float* const* keys, const float* dense, int64_t dense_stride,
+                                const void* mask, int64_t mask_stride, int32_t mask_kind,
+                                const int32_t* actions_in, uint64_t seed, uint64_t offset, uint32_t row_base,
+                                int32_t* actions_out, float* logprob, float* entropy, float* lse,
+                                float* head_entropy, void* stream);
+
+/* The gradient of sum_r g_logprob[r] logprob[r] + g_entropy[r] entropy[r]: g_dense [n_rows,
+ * g_dense_stride] like nmh_backward's g_logits over the dense heads, g_queries like queries,
+ * g_keys a HOST array of n_sets device pointers, g_keys[s] like keys[s] (16-byte aligned). Any of
+ * g_dense, g_queries, g_keys and each g_keys[s] may be NULL: that gradient is not computed. Every
+ * entry of every other one is written, zeros included; no atomics, the same bits on every run. */
+NMH_API int nmh_pointer_backward(const NmhHeads* hd, const NmhPointer* pt, int32_t n_rows, const float* queries,
+                                 const float* const* keys, const float* dense, int64_t dense_stride,
+                                 const void* mask, int64_t mask_stride, int32_t mask_kind,
+                                 const int32_t* actions, const float* lse, const float* head_entropy,
+                                 const float* g_logprob, const float* g_entropy, float* g_dense,
+                                 int64_t g_dense_stride, float* g_queries, float* const* g_keys, void* stream);
 
 NMH_API const char* nmh_last_error(void);
 /* "src=<hash of the sources the library was compiled from> arch=gfx950 fp_contract=off" */

@@ -1,6 +1,7 @@
 // heads.hip — libnmmo_heads.so (include/nmmo_heads.h): the masked multi-head categorical that
 // ends every reference policy (baseline_policy.py:245-262), fused. SPEC.md §15 holds the
-// semantics; DESIGN.md §3.12 the kernel notes.
+// semantics; DESIGN.md §3.12 the kernel notes. The pointer-head kernels further down (SPEC.md §18,
+// DESIGN.md §3.15) also compute the logits, query . key, of the heads that choose a candidate.
 //
 // Forward: one wave per row, 4 rows per 256-thread workgroup. The wave first stages its row in
 // LDS with coalesced dword loads -- logits[i] where the mask allows entry i, -inf elsewhere, as
@@ -120,6 +121,38 @@ __device__ __forceinline__ HeadOut head_forward(const float* s, int n, bool samp
   return o;
 }
 
+// Heads [k0, k1) of row r from their staged copies, which lie back to back from s: draws or reads
+// the action of each, stores its per-head outputs (a live wave's lane 0) and adds its logprob and
+// entropy to lp / ent.
+__device__ __forceinline__ void tile_heads(const float* s, const int32_t* dims, int k0, int k1, int n_heads, int64_t r,
+                                           bool live, const int32_t* __restrict__ actions_in, uint32_t seed_lo,
+                                           uint32_t seed_hi, uint32_t off_lo, uint32_t off_hi, uint32_t row_base,
+                                           int32_t* __restrict__ actions_out, float* __restrict__ lse,
+                                           float* __restrict__ head_entropy, float& lp, float& ent) {
+  const bool sample = actions_in == nullptr;
+  int o_s = 0;
+  for (int k = k0; k < k1; k++) {
+    const int n = dims[k];
+    float u = 0.f;
+    int a_in = 0;
+    if (sample) {
+      u = (float)(philox(row_base + (uint32_t)r, (uint32_t)k, off_lo, off_hi, seed_lo, seed_hi).x >> 8) * 0x1p-24f;
+    } else {
+      a_in = actions_in[r * n_heads + k];
+    }
+    const HeadOut o = head_forward(s + o_s, n, sample, u, a_in);
+    lp += o.logprob;
+    ent += o.entropy;
+    if (live && lane_id() == 0) {
+      const int64_t q = r * n_heads + k;
+      actions_out[q] = o.action;
+      lse[q] = o.lse;
+      head_entropy[q] = o.entropy;
+    }
+    o_s += n;
+  }
+}
+
 // tile: floats of LDS per wave = min(sum(dims), NMH_MAX_DIM), so any one head fits
 template <int MK>
 __global__ __launch_bounds__(64 * kRowsPerBlock) void nmh_forward_kernel(
@@ -136,7 +169,6 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void nmh_forward_kernel(
   const bool live = r0 < n_rows;
   const int64_t r = live ? r0 : n_rows - 1;
   const float* xrow = logits + r * ls;
-  const bool sample = actions_in == nullptr;
   float lp = 0.f, ent = 0.f;
   int k0 = 0, off = 0;
   while (k0 < hd.n_heads) {
@@ -162,27 +194,8 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void nmh_forward_kernel(
       }
     }
     __syncthreads();
-    int o_s = 0;
-    for (int k = k0; k < k1; k++) {
-      const int n = hd.dims[k];
-      float u = 0.f;
-      int a_in = 0;
-      if (sample) {
-        u = (float)(philox(row_base + (uint32_t)r, (uint32_t)k, off_lo, off_hi, seed_lo, seed_hi).x >> 8) * 0x1p-24f;
-      } else {
-        a_in = actions_in[r * hd.n_heads + k];
-      }
-      const HeadOut o = head_forward(s + o_s, n, sample, u, a_in);
-      lp += o.logprob;
-      ent += o.entropy;
-      if (live && lane_id() == 0) {
-        const int64_t q = r * hd.n_heads + k;
-        actions_out[q] = o.action;
-        lse[q] = o.lse;
-        head_entropy[q] = o.entropy;
-      }
-      o_s += n;
-    }
+    tile_heads(s, hd.dims, k0, k1, hd.n_heads, r, live, actions_in, seed_lo, seed_hi, off_lo, off_hi, row_base,
+               actions_out, lse, head_entropy, lp, ent);
     off += len;
     k0 = k1;
   }
@@ -222,6 +235,263 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void nmh_backward_kernel(
   }
 }
 
+// ---------------------------------------------------------------- pointer heads (SPEC.md §18)
+// The same wave-per-row kernels with one more way to fill the tile: a pointer head's logits are
+// dot products of the row's query with the row's candidate keys. The wave reads the head's mask
+// first and compacts the legal candidates' indices into a list in LDS (ballot + rank), then walks
+// the list, one candidate per 16-lane row and 16 bytes of a key row per lane, so the key rows of
+// illegal candidates are never touched and a head costs what its legal entries cost. The tile then
+// holds what nmh_forward_kernel would have staged from materialised logits, and head_forward runs
+// on it unchanged. DESIGN.md §3.15.
+
+// what the host works out once per call from NmhHeads + NmhPointer
+struct PtrPlan {
+  int32_t n_heads, n_sets, n_ptr, key_dim;
+  int32_t dims[NMH_MAX_HEADS];
+  int32_t off[NMH_MAX_HEADS];  // head k's first entry in the tile and in a mask row
+  int32_t set[NMH_MAX_HEADS];  // -1: dense, else its key set
+  int32_t src[NMH_MAX_HEADS];  // dense: its first column in a dense row; pointer: its query's index p
+  int32_t set_rows[NMH_MAX_SETS];
+  const float* keys[NMH_MAX_SETS];
+};
+struct KeyGrads {
+  float* p[NMH_MAX_SETS];
+};
+
+// LDS of one wave: the tile of `total` floats, then the index list of `max_rows` uint16
+__host__ __device__ inline int wave_lds_bytes(int total, int max_rows) { return (total * 4 + max_rows * 2 + 15) & ~15; }
+
+// orders this wave's LDS stores before its later LDS loads from other lanes
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// sum over each 16-lane row, in every lane of it: four row_ror steps (all lanes active)
+__device__ __forceinline__ float row16_sum(float x) {
+  x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x128, 0xF, 0xF, false));  // row_ror:8
+  x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x124, 0xF, 0xF, false));  // row_ror:4
+  x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x122, 0xF, 0xF, false));  // row_ror:2
+  x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x121, 0xF, 0xF, false));  // row_ror:1
+  return x;
+}
+
+// The mask of one pointer head's m candidates (mask entries mbase + [0, m)): s[j] = fill for every
+// j < m, and the legal j in ascending order in list[0, cnt). Returns cnt (wave-uniform).
+template <int MK>
+__device__ __forceinline__ int legal_list(const void* __restrict__ mask, int64_t mbase, int m, float* s, float fill,
+                                          uint16_t* list) {
+  constexpr int kU = 4;  // mask loads in flight per lane
+  int cnt = 0;
+  for (int b0 = 0; b0 < m; b0 += 64 * kU) {  // (wave-uniform trip count: every lane ballots)
+    const int j0 = b0 + lane_id();
+    bool l[kU];
+#pragma unroll
+    for (int u = 0; u < kU; u++) l[u] = legal_at<MK>(mask, mbase + min(j0 + 64 * u, m - 1));  // unconditional loads
+#pragma unroll
+    for (int u = 0; u < kU; u++) {
+      const int j = j0 + 64 * u;
+      const bool lg = l[u] && j < m;
+      const uint64_t b = __ballot(lg);
+      if (j < m) s[j] = fill;
+      if (lg) list[cnt + __popcll(b & lanes_below())] = (uint16_t)j;
+      cnt += __popcll(b);
+    }
+  }
+  return cnt;
+}
+
+// the query of one pointer head: lane l of every 16-lane row holds floats [4 (l + 16 c), + 4)
+template <int NC>
+__device__ __forceinline__ void load_query(const float* __restrict__ q, int D, float4 (&out)[NC]) {
+#pragma unroll
+  for (int c = 0; c < NC; c++) {
+    const int d4 = (lane_id() & 15) + 16 * c;
+    out[c] = 4 * d4 < D ? reinterpret_cast<const float4*>(q)[d4] : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+}
+
+// Walks the listed candidates of one head: 16-lane row g of the wave takes list[i0 + 4 u + g], each
+// lane loads 16 B of that key row per 64-float chunk (NC chunks cover D), kU candidates per row in
+// flight. f(j, x_j, the lane's piece of key row j) runs in all 16 lanes of the row that took j.
+template <int NC, class Fn>
+__device__ __forceinline__ void for_listed_keys(const uint16_t* list, int cnt, const float* __restrict__ krow, int D,
+                                                const float4 (&q)[NC], Fn&& f) {
+  constexpr int kU = NC == 1 ? 4 : 2;
+  const int g = lane_id() >> 4, l = lane_id() & 15, nd4 = D >> 2;
+  const float4* k4 = reinterpret_cast<const float4*>(krow);
+  for (int i0 = 0; i0 < cnt; i0 += 4 * kU) {
+    int j[kU];
+    float4 kv[kU][NC];
+#pragma unroll
+    for (int u = 0; u < kU; u++) {
+      const int i = i0 + 4 * u + g;
+      j[u] = i < cnt ? (int)list[i] : -1;
+    }
+#pragma unroll
+    for (int u = 0; u < kU; u++) {
+#pragma unroll
+      for (int c = 0; c < NC; c++) {
+        const int d4 = l + 16 * c;
+        kv[u][c] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (j[u] >= 0 && d4 < nd4) kv[u][c] = k4[(int64_t)j[u] * nd4 + d4];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kU; u++) {
+      float acc = 0.f;
+#pragma unroll
+      for (int c = 0; c < NC; c++) {
+        acc = fmaf(kv[u][c].x, q[c].x, acc);
+        acc = fmaf(kv[u][c].y, q[c].y, acc);
+        acc = fmaf(kv[u][c].z, q[c].z, acc);
+        acc = fmaf(kv[u][c].w, q[c].w, acc);
+      }
+      const float x = row16_sum(acc);
+      if (j[u] >= 0) f(j[u], x, kv[u]);
+    }
+  }
+}
+
+template <int MK, int NC>
+__global__ __launch_bounds__(64 * kRowsPerBlock) void nmh_pointer_forward_kernel(
+    PtrPlan pl, int n_rows, int total, int wave_bytes, const float* __restrict__ queries,
+    const float* __restrict__ dense, int64_t ds, const void* __restrict__ mask, int64_t ms,
+    const int32_t* __restrict__ actions_in, uint32_t seed_lo, uint32_t seed_hi, uint32_t off_lo, uint32_t off_hi,
+    uint32_t row_base, int32_t* __restrict__ actions_out, float* __restrict__ logprob, float* __restrict__ entropy,
+    float* __restrict__ lse, float* __restrict__ head_entropy) {
+  extern __shared__ float staged[];
+  const int w = __builtin_amdgcn_readfirstlane(wave_id());
+  const int64_t r = (int64_t)blockIdx.x * kRowsPerBlock + w;
+  if (r >= n_rows) return;  // (waves share nothing: no workgroup barrier below)
+  float* s = reinterpret_cast<float*>(reinterpret_cast<char*>(staged) + (size_t)w * wave_bytes);
+  uint16_t* list = reinterpret_cast<uint16_t*>(s + total);
+  const int D = pl.key_dim;
+  for (int k = 0; k < pl.n_heads; k++) {
+    const int n = pl.dims[k], off = pl.off[k], set = pl.set[k];
+    const int64_t mbase = r * ms + off;
+    if (set < 0) {  // dense: the given logit where legal
+      const float* x = dense + r * ds + pl.src[k];
+      for (int i = lane_id(); i < n; i += 64) s[off + i] = legal_at<MK>(mask, mbase + i) ? x[i] : -INFINITY;
+      continue;
+    }
+    const int m = n - 1;
+    const int cnt = legal_list<MK>(mask, mbase, m, s + off, -INFINITY, list);
+    if (lane_id() == 0) s[off + m] = legal_at<MK>(mask, mbase + m) ? 0.f : -INFINITY;  // the no-op entry
+    wave_sync();
+    float4 q[NC];
+    load_query<NC>(queries + (r * pl.n_ptr + pl.src[k]) * D, D, q);
+    for_listed_keys<NC>(list, cnt, pl.keys[set] + r * m * D, D, q, [&](int j, float x, const float4(&)[NC]) {
+      if ((lane_id() & 15) == 0) s[off + j] = x;
+    });
+    wave_sync();  // the next head rebuilds the list
+  }
+  wave_sync();
+  float lp = 0.f, ent = 0.f;
+  tile_heads(s, pl.dims, 0, pl.n_heads, pl.n_heads, r, true, actions_in, seed_lo, seed_hi, off_lo, off_hi, row_base,
+             actions_out, lse, head_entropy, lp, ent);
+  if (lane_id() == 0) {
+    logprob[r] = lp;
+    entropy[r] = ent;
+  }
+}
+
+// Pass 1, per head: g_j as in nmh_backward_kernel. A dense head's goes straight to g_dense. A pointer
+// head recomputes x_j from the key row it has just loaded, keeps g_j in the tile (0 off the legal
+// set) and adds g_j K_j to the query's gradient from the same registers. Pass 2, per key set: every
+// gK row, the sum over the set's heads in head order of g_j Q, as float4 stores along D.
+template <int MK, int NC>
+__global__ __launch_bounds__(64 * kRowsPerBlock) void nmh_pointer_backward_kernel(
+    PtrPlan pl, int n_rows, int total, int wave_bytes, const float* __restrict__ queries,
+    const float* __restrict__ dense, int64_t ds, const void* __restrict__ mask, int64_t ms,
+    const int32_t* __restrict__ actions, const float* __restrict__ lse, const float* __restrict__ head_entropy,
+    const float* __restrict__ g_logprob, const float* __restrict__ g_entropy, float* __restrict__ g_dense, int64_t gds,
+    float* __restrict__ g_queries, KeyGrads gk) {
+  extern __shared__ float staged[];
+  const int w = __builtin_amdgcn_readfirstlane(wave_id());
+  const int64_t r = (int64_t)blockIdx.x * kRowsPerBlock + w;
+  if (r >= n_rows) return;
+  float* s = reinterpret_cast<float*>(reinterpret_cast<char*>(staged) + (size_t)w * wave_bytes);
+  uint16_t* list = reinterpret_cast<uint16_t*>(s + total);
+  const int D = pl.key_dim, nd4 = D >> 2;
+  const float glp = g_logprob ? g_logprob[r] : 0.f, gen = g_entropy ? g_entropy[r] : 0.f;
+  for (int k = 0; k < pl.n_heads; k++) {
+    const int n = pl.dims[k], off = pl.off[k], set = pl.set[k];
+    const int64_t mbase = r * ms + off, hq = r * pl.n_heads + k;
+    const int a = actions[hq];
+    const float L = lse[hq], H = head_entropy[hq];
+    auto grad = [&](int i, float x) {
+      const float logp = x - L;
+      const float p = expf(logp);
+      return glp * ((i == a ? 1.f : 0.f) - p) - gen * (p * (logp + H));
+    };
+    if (set < 0) {
+      if (!g_dense) continue;
+      const float* x = dense + r * ds + pl.src[k];
+      float* gx = g_dense + r * gds + pl.src[k];
+      for (int i = lane_id(); i < n; i += 64) {
+        const bool l = legal_at<MK>(mask, mbase + i);
+        const float g = grad(i, x[i]);
+        gx[i] = l ? g : 0.f;
+      }
+      continue;
+    }
+    if (!g_queries && !gk.p[set]) continue;
+    const int m = n - 1;
+    const int cnt = legal_list<MK>(mask, mbase, m, s + off, 0.f, list);
+    wave_sync();
+    float4 q[NC], gq[NC];
+    load_query<NC>(queries + (r * pl.n_ptr + pl.src[k]) * D, D, q);
+#pragma unroll
+    for (int c = 0; c < NC; c++) gq[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for_listed_keys<NC>(list, cnt, pl.keys[set] + r * m * D, D, q, [&](int j, float x, const float4(&kv)[NC]) {
+      const float g = grad(j, x);
+      if ((lane_id() & 15) == 0) s[off + j] = g;
+#pragma unroll
+      for (int c = 0; c < NC; c++) {
+        gq[c].x = fmaf(g, kv[c].x, gq[c].x);
+        gq[c].y = fmaf(g, kv[c].y, gq[c].y);
+        gq[c].z = fmaf(g, kv[c].z, gq[c].z);
+        gq[c].w = fmaf(g, kv[c].w, gq[c].w);
+      }
+    });
+    if (g_queries) {  // the four 16-lane rows' partial sums, in a fixed order
+      float4* out = reinterpret_cast<float4*>(g_queries + (r * pl.n_ptr + pl.src[k]) * D);
+#pragma unroll
+      for (int c = 0; c < NC; c++) {
+        float4 v = gq[c];
+        v.x += __shfl_xor(v.x, 16), v.y += __shfl_xor(v.y, 16), v.z += __shfl_xor(v.z, 16), v.w += __shfl_xor(v.w, 16);
+        v.x += __shfl_xor(v.x, 32), v.y += __shfl_xor(v.y, 32), v.z += __shfl_xor(v.z, 32), v.w += __shfl_xor(v.w, 32);
+        const int d4 = lane_id() + 16 * c;
+        if (lane_id() < 16 && d4 < nd4) out[d4] = v;
+      }
+    }
+    wave_sync();
+  }
+  for (int set = 0; set < pl.n_sets; set++) {
+    if (!gk.p[set]) continue;
+    const int n4 = pl.set_rows[set] * nd4;  // float4s of this row's gK: <= 2047 * 64
+    float4* out = reinterpret_cast<float4*>(gk.p[set]) + r * n4;
+    for (int f = lane_id(); f < n4; f += 64) {
+      const int j = f / nd4, d4 = f - j * nd4;
+      float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int k = 0; k < pl.n_heads; k++) {
+        if (pl.set[k] != set) continue;
+        const float g = s[pl.off[k] + j];
+        if (g != 0.f) {  // (most entries: illegal, g = 0; the query is then not fetched)
+          const float4 qv = reinterpret_cast<const float4*>(queries + (r * pl.n_ptr + pl.src[k]) * D)[d4];
+          acc.x = fmaf(g, qv.x, acc.x);
+          acc.y = fmaf(g, qv.y, acc.y);
+          acc.z = fmaf(g, qv.z, acc.z);
+          acc.w = fmaf(g, qv.w, acc.w);
+        }
+      }
+      out[f] = acc;
+    }
+  }
+}
+
 // the argument checks both entry points share; *total gets sum(dims)
 int check_args(const char* fn, const NmhHeads* hd, int32_t n_rows, const void* logits, int64_t ls, const void* mask,
                int64_t ms, int32_t mask_kind, int64_t* total) {
@@ -248,6 +518,94 @@ int launched(const char* fn) {
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? NMH_OK : fail(NMH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
 }
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// The argument checks the two pointer entry points share (SPEC.md §18, "Limits"); fills the plan,
+// *dense_total (the dense heads' columns) and *max_rows (the largest set_rows in use).
+int check_pointer(const char* fn, const NmhHeads* hd, const NmhPointer* pt, int32_t n_rows, const float* queries,
+                  const float* const* keys, const float* dense, int64_t ds, const void* mask, int64_t ms,
+                  int32_t mask_kind, PtrPlan* pl, int64_t* total, int64_t* dense_total, int* max_rows) {
+  if (!hd) return fail(NMH_E_INVALID, "%s: hd is NULL", fn);
+  if (!pt) return fail(NMH_E_INVALID, "%s: pt is NULL", fn);
+  if (hd->n_heads < 1 || hd->n_heads > NMH_MAX_HEADS)
+    return fail(NMH_E_INVALID, "%s: n_heads %d outside 1..%d", fn, hd->n_heads, NMH_MAX_HEADS);
+  if (pt->n_sets < 0 || pt->n_sets > NMH_MAX_SETS)
+    return fail(NMH_E_INVALID, "%s: n_sets %d outside 0..%d", fn, pt->n_sets, NMH_MAX_SETS);
+  const int D = pt->key_dim;
+  if (pt->n_sets > 0 && (D < 4 || D > NMH_MAX_KEY_DIM || D % 4))
+    return fail(NMH_E_INVALID, "%s: key_dim %d is not a multiple of 4 in 4..%d", fn, D, NMH_MAX_KEY_DIM);
+  for (int s = 0; s < pt->n_sets; s++)
+    if (pt->set_rows[s] < 1 || pt->set_rows[s] >= NMH_MAX_DIM)
+      return fail(NMH_E_INVALID, "%s: set_rows[%d] = %d outside 1..%d", fn, s, pt->set_rows[s], NMH_MAX_DIM - 1);
+  *pl = PtrPlan{};
+  pl->n_heads = hd->n_heads;
+  pl->n_sets = pt->n_sets;
+  pl->key_dim = D;
+  int64_t sum = 0, dsum = 0;
+  unsigned used = 0;
+  *max_rows = 0;
+  for (int k = 0; k < hd->n_heads; k++) {
+    const int n = hd->dims[k], s = pt->head_set[k];
+    if (n < 1 || n > NMH_MAX_DIM)
+      return fail(NMH_E_INVALID, "%s: dims[%d] = %d outside 1..%d", fn, k, n, NMH_MAX_DIM);
+    if (s < -1 || s >= pt->n_sets)
+      return fail(NMH_E_INVALID, "%s: head_set[%d] = %d outside -1..%d", fn, k, s, pt->n_sets - 1);
+    if (s >= 0 && n != pt->set_rows[s] + 1)
+      return fail(NMH_E_INVALID, "%s: dims[%d] = %d is not set_rows[%d] + 1 = %d", fn, k, n, s, pt->set_rows[s] + 1);
+    pl->dims[k] = n;
+    pl->off[k] = (int32_t)sum;
+    pl->set[k] = s;
+    if (s < 0) {
+      pl->src[k] = (int32_t)dsum;
+      dsum += n;
+    } else {
+      pl->src[k] = pl->n_ptr++;
+      used |= 1u << s;
+      *max_rows = std::max(*max_rows, n - 1);
+    }
+    sum += n;
+  }
+  if (sum > NMH_MAX_DIM)
+    return fail(NMH_E_INVALID, "%s: sum(dims) %lld exceeds NMH_MAX_DIM %d", fn, (long long)sum, NMH_MAX_DIM);
+  for (int s = 0; s < pt->n_sets; s++)
+    if (!(used >> s & 1u)) return fail(NMH_E_INVALID, "%s: no head uses key set %d (head_set)", fn, s);
+  if (n_rows < 0) return fail(NMH_E_INVALID, "%s: n_rows %d is negative", fn, n_rows);
+  if (!mask) return fail(NMH_E_INVALID, "%s: mask is NULL", fn);
+  if (mask_kind != NMH_MASK_F32 && mask_kind != NMH_MASK_U8)
+    return fail(NMH_E_INVALID, "%s: unknown mask_kind %d", fn, mask_kind);
+  if (ms < sum) return fail(NMH_E_INVALID, "%s: mask_stride %lld < sum(dims) %lld", fn, (long long)ms, (long long)sum);
+  if (dsum > 0 && !dense) return fail(NMH_E_INVALID, "%s: dense is NULL with dense heads", fn);
+  if (dsum > 0 && ds < dsum)
+    return fail(NMH_E_INVALID, "%s: dense_stride %lld < the dense heads' %lld columns", fn, (long long)ds, (long long)dsum);
+  if (pl->n_ptr > 0) {
+    if (!queries || !keys) return fail(NMH_E_INVALID, "%s: queries or keys is NULL with pointer heads", fn);
+    if (!aligned16(queries)) return fail(NMH_E_INVALID, "%s: queries is not 16-byte aligned", fn);
+    for (int s = 0; s < pt->n_sets; s++) {
+      if (!keys[s]) return fail(NMH_E_INVALID, "%s: keys[%d] is NULL", fn, s);
+      if (!aligned16(keys[s])) return fail(NMH_E_INVALID, "%s: keys[%d] is not 16-byte aligned", fn, s);
+      pl->set_rows[s] = pt->set_rows[s];
+      pl->keys[s] = keys[s];
+    }
+  }
+  *total = sum;
+  *dense_total = dsum;
+  return NMH_OK;
+}
+
+// launches K<mask kind, 64-float chunks of a key row> on n_rows rows
+#define NMH_POINTER_LAUNCH(K, fn, ...)                                                                           \
+  do {                                                                                                           \
+    const dim3 grid((unsigned)((n_rows + kRowsPerBlock - 1) / kRowsPerBlock)), block(64 * kRowsPerBlock);        \
+    const int wave_bytes = wave_lds_bytes((int)total, max_rows), nc = (pl.key_dim + 63) / 64;                    \
+    const bool f32 = mask_kind == NMH_MASK_F32;                                                                  \
+    auto* kern = nc <= 1   ? (f32 ? K<NMH_MASK_F32, 1> : K<NMH_MASK_U8, 1>)                                      \
+                 : nc == 2 ? (f32 ? K<NMH_MASK_F32, 2> : K<NMH_MASK_U8, 2>)                                      \
+                           : (f32 ? K<NMH_MASK_F32, 4> : K<NMH_MASK_U8, 4>);                                     \
+    hipLaunchKernelGGL(kern, grid, block, (size_t)kRowsPerBlock* wave_bytes, static_cast<hipStream_t>(stream), pl, \
+                       n_rows, (int)total, wave_bytes, __VA_ARGS__);                                             \
+    return launched(fn);                                                                                         \
+  } while (0)
 
 }  // namespace
 
@@ -292,6 +650,57 @@ int nmh_backward(const NmhHeads* hd, int32_t n_rows, const float* logits, int64_
   hipLaunchKernelGGL(kern, grid, block, 0, static_cast<hipStream_t>(stream), *hd, n_rows, logits, logits_stride, mask,
                      mask_stride, actions, lse, head_entropy, g_logprob, g_entropy, g_logits, g_stride);
   return launched("nmh_backward");
+}
+
+int nmh_pointer_forward(const NmhHeads* hd, const NmhPointer* pt, int32_t n_rows, const float* queries,
+                        const float* const* keys, const float* dense, int64_t dense_stride, const void* mask,
+                        int64_t mask_stride, int32_t mask_kind, const int32_t* actions_in, uint64_t seed,
+                        uint64_t offset, uint32_t row_base, int32_t* actions_out, float* logprob, float* entropy,
+                        float* lse, float* head_entropy, void* stream) {
+  PtrPlan pl;
+  int64_t total, dense_total;
+  int max_rows;
+  const int rc = check_pointer("nmh_pointer_forward", hd, pt, n_rows, queries, keys, dense, dense_stride, mask,
+                               mask_stride, mask_kind, &pl, &total, &dense_total, &max_rows);
+  if (rc != NMH_OK) return rc;
+  if (!actions_out || !logprob || !entropy || !lse || !head_entropy)
+    return fail(NMH_E_INVALID, "nmh_pointer_forward: an output pointer is NULL");
+  if (n_rows == 0) return NMH_OK;
+  NMH_POINTER_LAUNCH(nmh_pointer_forward_kernel, "nmh_pointer_forward", queries, dense, dense_stride, mask,
+                     mask_stride, actions_in, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)offset,
+                     (uint32_t)(offset >> 32), row_base, actions_out, logprob, entropy, lse, head_entropy);
+}
+
+int nmh_pointer_backward(const NmhHeads* hd, const NmhPointer* pt, int32_t n_rows, const float* queries,
+                         const float* const* keys, const float* dense, int64_t dense_stride, const void* mask,
+                         int64_t mask_stride, int32_t mask_kind, const int32_t* actions, const float* lse,
+                         const float* head_entropy, const float* g_logprob, const float* g_entropy, float* g_dense,
+                         int64_t g_dense_stride, float* g_queries, float* const* g_keys, void* stream) {
+  PtrPlan pl;
+  int64_t total, dense_total;
+  int max_rows;
+  const int rc = check_pointer("nmh_pointer_backward", hd, pt, n_rows, queries, keys, dense, dense_stride, mask,
+                               mask_stride, mask_kind, &pl, &total, &dense_total, &max_rows);
+  if (rc != NMH_OK) return rc;
+  if (!actions || !lse || !head_entropy)
+    return fail(NMH_E_INVALID, "nmh_pointer_backward: actions, lse or head_entropy is NULL");
+  if (g_dense && g_dense_stride < dense_total)
+    return fail(NMH_E_INVALID, "nmh_pointer_backward: g_dense_stride %lld < the dense heads' %lld columns",
+                (long long)g_dense_stride, (long long)dense_total);
+  if (g_queries && !aligned16(g_queries))
+    return fail(NMH_E_INVALID, "nmh_pointer_backward: g_queries is not 16-byte aligned");
+  KeyGrads gk{};
+  for (int s = 0; g_keys && s < pl.n_sets; s++) {
+    if (!aligned16(g_keys[s]))
+      return fail(NMH_E_INVALID, "nmh_pointer_backward: g_keys[%d] is not 16-byte aligned", s);
+    gk.p[s] = g_keys[s];
+  }
+  if (dense_total == 0) g_dense = nullptr;
+  if (pl.n_ptr == 0) g_queries = nullptr;
+  if (n_rows == 0) return NMH_OK;
+  NMH_POINTER_LAUNCH(nmh_pointer_backward_kernel, "nmh_pointer_backward", queries, dense, dense_stride, mask,
+                     mask_stride, actions, lse, head_entropy, g_logprob, g_entropy, g_dense, g_dense_stride,
+                     g_queries, gk);
 }
 
 }  // extern "C"

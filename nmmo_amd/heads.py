@@ -5,8 +5,10 @@
     _, logprob, entropy = masked_heads(logits, obs, dims, action=action)  # evaluate, differentiable
 
 replaces the per-head `masked_fill(mask == 0, -1e9)` + `Categorical` loop of the reference's
-policies (baseline_policy.py:245-262) by one kernel forward and one backward. There is no torch
-fallback: a missing or stale library is an error.
+policies (baseline_policy.py:245-262) by one kernel forward and one backward. `pointer_heads`
+(nmh_pointer_forward / nmh_pointer_backward, SPEC.md §18) also computes the logits of the
+reference's pointer heads, query . key over the row's candidates, inside that kernel. There is no
+torch fallback: a missing or stale library is an error.
 
 torch is imported first so that the library binds to the HIP runtime torch loaded (see
 `_loader.py`): tensors' device pointers and torch's streams are then valid inside the library.
@@ -20,8 +22,10 @@ import os
 from . import _loader, build
 
 LIB_PATH = os.environ.get("NMMO_HEADS_LIB", build.lib_path("heads"))
-SYMBOLS = ["nmh_forward", "nmh_backward", "nmh_last_error", "nmh_build_info"]
+SYMBOLS = ["nmh_forward", "nmh_backward", "nmh_pointer_forward", "nmh_pointer_backward", "nmh_last_error",
+           "nmh_build_info"]
 MAX_HEADS, MAX_DIM = 16, 2048
+MAX_SETS, MAX_KEY_DIM = 4, 256
 MASK_F32, MASK_U8 = 0, 1
 NMH_OK, NMH_E_INVALID, NMH_E_HIP = 0, -1, -2
 _lib = None
@@ -35,9 +39,18 @@ class NmhHeads(ctypes.Structure):
     _fields_ = [("n_heads", ctypes.c_int32), ("dims", ctypes.c_int32 * MAX_HEADS)]
 
 
+class NmhPointer(ctypes.Structure):
+    _fields_ = [("n_sets", ctypes.c_int32), ("key_dim", ctypes.c_int32), ("set_rows", ctypes.c_int32 * MAX_SETS),
+                ("head_set", ctypes.c_int32 * MAX_HEADS)]
+
+
 def declare(L):
     vp, i32, i64, u64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
-    hp = ctypes.POINTER(NmhHeads)
+    hp, pp, kp = ctypes.POINTER(NmhHeads), ctypes.POINTER(NmhPointer), ctypes.POINTER(ctypes.c_void_p)
+    L.nmh_pointer_forward.argtypes = [hp, pp, i32, vp, kp, vp, i64, vp, i64, i32, vp, u64, u64, ctypes.c_uint32,
+                                      vp, vp, vp, vp, vp, vp]
+    L.nmh_pointer_backward.argtypes = [hp, pp, i32, vp, kp, vp, i64, vp, i64, i32, vp, vp, vp, vp, vp, vp, i64, vp,
+                                       kp, vp]
     L.nmh_forward.argtypes = [hp, i32, vp, i64, vp, i64, i32, vp, u64, u64, ctypes.c_uint32, vp, vp, vp, vp, vp, vp]
     L.nmh_backward.argtypes = [hp, i32, vp, i64, vp, i64, i32, vp, vp, vp, vp, vp, vp, i64, vp]
 
@@ -174,3 +187,168 @@ def masked_heads(logits, mask, dims, action=None, *, seed: int = 0, offset: int 
     differentiable with respect to logits.
     """
     return masked_heads_full(logits, mask, dims, action, seed=seed, offset=offset, row_base=row_base)[:3]
+
+
+# ---------------------------------------------------------------- pointer heads (SPEC.md §18)
+def pointer_struct(dims, head_set, set_rows, key_dim) -> NmhPointer:
+    head_set, set_rows = [int(s) for s in head_set], [int(m) for m in set_rows]
+    if len(head_set) != len(dims):
+        raise ValueError(f"head_set has {len(head_set)} entries for {len(dims)} heads")
+    if len(set_rows) > MAX_SETS:
+        raise ValueError(f"at most {MAX_SETS} key sets, got {len(set_rows)}")
+    if set_rows and (key_dim % 4 or not 4 <= key_dim <= MAX_KEY_DIM):
+        raise ValueError(f"the key width must be a multiple of 4 in 4..{MAX_KEY_DIM}, got {key_dim}")
+    for k, s in enumerate(head_set):
+        if not -1 <= s < len(set_rows):
+            raise ValueError(f"head_set[{k}] = {s} names none of the {len(set_rows)} key sets")
+        if s >= 0 and int(dims[k]) != set_rows[s] + 1:
+            raise ValueError(f"head {k} has {dims[k]} entries, key set {s} has {set_rows[s]} rows + the no-op")
+    if set(range(len(set_rows))) - set(head_set):
+        raise ValueError(f"no head uses key set(s) {sorted(set(range(len(set_rows))) - set(head_set))}")
+    if sum(int(d) for d in dims) > MAX_DIM:
+        raise ValueError(f"the heads' sizes sum to {sum(dims)}, more than {MAX_DIM}")
+    pt = NmhPointer()
+    pt.n_sets, pt.key_dim = len(set_rows), int(key_dim)
+    for s, m in enumerate(set_rows):
+        pt.set_rows[s] = m
+    for k, s in enumerate(head_set):
+        pt.head_set[k] = s
+    return pt
+
+
+def _dense16(t):
+    """t, detached, as a contiguous 16-byte aligned tensor (copied only if it is not one)."""
+    t = t.detach().contiguous()
+    return t.clone() if t.data_ptr() % 16 else t
+
+
+def _key_array(tensors):
+    return (ctypes.c_void_p * max(1, len(tensors)))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def _make_pointer_function():
+    import torch
+
+    class PointerHeads(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, queries, dense, mask, dims, head_set, action, seed, offset, row_base, *keys):
+            hd = heads_struct(dims)
+            dims, head_set = [int(d) for d in dims], [int(s) for s in head_set]
+            if len(head_set) != len(dims):
+                raise ValueError(f"head_set has {len(head_set)} entries for {len(dims)} heads")
+            total, n_ptr = sum(dims), sum(s >= 0 for s in head_set)
+            n_dense = sum(d for d, s in zip(dims, head_set) if s < 0)
+            if not mask.is_cuda:
+                raise HeadsError("pointer_heads runs on the GPU: every input must be a device tensor")
+            n, dev = mask.shape[0], mask.device
+            for s, kt in enumerate(keys):
+                if not kt.is_cuda or kt.dtype != torch.float32 or kt.dim() != 3 or kt.shape[0] != n:
+                    raise ValueError(f"keys[{s}] must be float32 [{n}, m, D] on the GPU, got {kt.dtype} {tuple(kt.shape)}")
+            key_dim = keys[0].shape[2] if keys else 0
+            if any(kt.shape[2] != key_dim for kt in keys):
+                raise ValueError(f"every key set must have the same width, got {[kt.shape[2] for kt in keys]}")
+            if n_ptr:
+                if queries is None or not queries.is_cuda or queries.dtype != torch.float32 or \
+                        tuple(queries.shape) != (n, n_ptr, key_dim):
+                    raise ValueError(f"queries must be float32 [{n}, {n_ptr}, {key_dim}] on the GPU, got "
+                                     f"{None if queries is None else (queries.dtype, tuple(queries.shape))}")
+                queries = _dense16(queries)
+            else:
+                queries = None
+            if n_dense:
+                if dense is None or not dense.is_cuda or dense.dtype != torch.float32 or \
+                        tuple(dense.shape) != (n, n_dense):
+                    raise ValueError(f"dense_logits must be float32 [{n}, {n_dense}] on the GPU, got "
+                                     f"{None if dense is None else (dense.dtype, tuple(dense.shape))}")
+                dense = dense.detach().contiguous()
+            else:
+                dense = None
+            keys = [_dense16(kt) for kt in keys]
+            pt = pointer_struct(dims, head_set, [kt.shape[1] for kt in keys], key_dim)
+            mask, mptr, mstride, kind = _mask_arg(mask, n, total)
+            a_in = None
+            if action is not None:
+                if tuple(action.shape) != (n, hd.n_heads):
+                    raise ValueError(f"action must be [{n}, {hd.n_heads}], got {tuple(action.shape)}")
+                a_in = action.to(device=dev, dtype=torch.int32).contiguous()
+            a_out = torch.empty((n, hd.n_heads), dtype=torch.int32, device=dev)
+            logprob = torch.empty(n, dtype=torch.float32, device=dev)
+            entropy = torch.empty(n, dtype=torch.float32, device=dev)
+            lse = torch.empty((n, hd.n_heads), dtype=torch.float32, device=dev)
+            hent = torch.empty((n, hd.n_heads), dtype=torch.float32, device=dev)
+            with torch.cuda.device(dev):
+                check(lib().nmh_pointer_forward(
+                    ctypes.byref(hd), ctypes.byref(pt), n, None if queries is None else queries.data_ptr(),
+                    _key_array(keys), None if dense is None else dense.data_ptr(), n_dense, mptr, mstride, kind,
+                    None if a_in is None else a_in.data_ptr(), int(seed) & (2**64 - 1), int(offset) & (2**64 - 1),
+                    int(row_base) & 0xFFFFFFFF, a_out.data_ptr(), logprob.data_ptr(), entropy.data_ptr(),
+                    lse.data_ptr(), hent.data_ptr(), _stream()), "nmh_pointer_forward")
+            ctx.hd, ctx.pt, ctx.kind, ctx.n_dense = hd, pt, kind, n_dense
+            ctx.has = (queries is not None, dense is not None)
+            ctx.set_materialize_grads(False)
+            ctx.save_for_backward(mask, a_out, lse, hent, *[t for t in (queries, dense) if t is not None], *keys)
+            ctx.mark_non_differentiable(a_out, lse, hent)
+            return a_out, logprob, entropy, lse, hent
+
+        @staticmethod
+        def backward(ctx, _ga, g_logprob, g_entropy, _gl, _gh):
+            mask, actions, lse, hent, *rest = ctx.saved_tensors
+            queries = rest.pop(0) if ctx.has[0] else None
+            dense = rest.pop(0) if ctx.has[1] else None
+            keys = rest
+            hd, pt, n, dev = ctx.hd, ctx.pt, mask.shape[0], mask.device
+            total = sum(hd.dims[:hd.n_heads])
+            need = ctx.needs_input_grad  # a gradient nobody asked for is a NULL pointer: not computed
+            g_q = torch.empty_like(queries) if queries is not None and need[0] else None
+            g_d = torch.empty_like(dense) if dense is not None and need[1] else None
+            g_k = [torch.empty_like(kt) if need[9 + s] else None for s, kt in enumerate(keys)]
+            glp = None if g_logprob is None else g_logprob.to(torch.float32).contiguous()
+            gen = None if g_entropy is None else g_entropy.to(torch.float32).contiguous()
+            with torch.cuda.device(dev):
+                check(lib().nmh_pointer_backward(
+                    ctypes.byref(hd), ctypes.byref(pt), n, None if queries is None else queries.data_ptr(),
+                    _key_array(keys), None if dense is None else dense.data_ptr(), ctx.n_dense, mask.data_ptr(),
+                    max(mask.stride(0), total), ctx.kind, actions.data_ptr(), lse.data_ptr(), hent.data_ptr(),
+                    None if glp is None else glp.data_ptr(), None if gen is None else gen.data_ptr(),
+                    None if g_d is None else g_d.data_ptr(), ctx.n_dense, None if g_q is None else g_q.data_ptr(),
+                    _key_array(g_k), _stream()), "nmh_pointer_backward")
+            return (g_q, g_d, None, None, None, None, None, None, None, *g_k)
+
+    return PointerHeads
+
+
+_pointer_function = None
+
+
+def pointer_heads_full(queries, keys, head_set, dense_logits, mask, dims, action=None, *, seed: int = 0,
+                       offset: int = 0, row_base: int = 0):
+    """`pointer_heads` plus the per-head saved values: (action, logprob, entropy, lse [N, H],
+    head_entropy [N, H])."""
+    global _pointer_function
+    if _pointer_function is None:
+        _pointer_function = _make_pointer_function()
+    a, logprob, entropy, lse, hent = _pointer_function.apply(
+        queries, dense_logits, mask, tuple(dims), tuple(head_set), action, seed, offset, row_base, *keys)
+    return (a if action is None else action), logprob, entropy, lse, hent
+
+
+def pointer_heads(queries, keys, head_set, dense_logits, mask, dims, action=None, *, seed: int = 0, offset: int = 0,
+                  row_base: int = 0):
+    """Masked categorical heads of which some are pointer heads, in one kernel (SPEC.md §18): the
+    decoders of the reference's policies (baseline_policy.py:222-230) without the zero-padded copy
+    of the embeddings, the batched mat-vec over every candidate and the logits tensor.
+
+    dims, head_set: per head its size and -1 (dense: its logits are given) or the index s of the
+        key set it points into; then dims[k] == keys[s].shape[1] + 1, the last entry being the
+        no-op with logit 0.
+    queries: float32 [N, P, D], one query per pointer head in head order (None if P == 0).
+    keys: a sequence of float32 [N, m_s, D]. Head k's logit of candidate j < m_s is
+        keys[s][r, j] . queries[r, p]; rows of illegal candidates are never read.
+    dense_logits: float32 [N, sum of the dense heads' dims] in head order, or None.
+    mask, action, seed, offset, row_base: as for `masked_heads`; mask columns cover all heads.
+    Returns (action, logprob [N], entropy [N]); logprob and entropy are differentiable with respect
+    to queries, every keys tensor and dense_logits, and a gradient that nothing requires is not
+    computed. Non-contiguous or misaligned inputs are copied; there is no torch fallback.
+    """
+    return pointer_heads_full(queries, keys, head_set, dense_logits, mask, dims, action, seed=seed, offset=offset,
+                              row_base=row_base)[:3]

@@ -14,6 +14,8 @@ The policy networks themselves are out of scope (consumers of the
 `MaskedLinearAgent` is a minimal stand-in with the reference policies' call convention —
 `agent(obs, action=None) -> (action, logprob, entropy, value)` with every head's logits masked
 by the obs ActionTargets (baseline_policy.py:245-262) — so the loop can be exercised and timed.
+`PointerMaskedAgent` is the same stand-in with the reference decoders' pointer heads
+(baseline_policy.py:222-230; SPEC.md §18).
 `RecurrentMaskedAgent` is the same stand-in with an LSTM between encoder and heads and the
 reference's recurrent convention, `agent(obs, state, action=None) -> (..., state)`: for an agent
 with an `.lstm` attribute the loop carries one LSTM state per agent slot through `evaluate()` and
@@ -97,7 +99,10 @@ class MaskedLinearAgent(nn.Module):
 
     def heads(self, h: torch.Tensor, obs: torch.Tensor, action: torch.Tensor | None = None):
         """The masked action heads and the value head on the hidden rows `h` of the rows `obs`."""
-        logits = self.actor(h)
+        return self.masked(self.actor(h), h, obs, action)
+
+    def masked(self, logits: torch.Tensor, h: torch.Tensor, obs: torch.Tensor, action: torch.Tensor | None = None):
+        """`heads` from the heads' concatenated logits on."""
         if self.fused_heads:
             from .heads import masked_heads
 
@@ -116,6 +121,75 @@ class MaskedLinearAgent(nn.Module):
             logp = logp + dist.log_prob(a)
             ent = ent + dist.entropy()
         return torch.stack(acts, 1), logp, ent, self.value(h)
+
+
+def pointer_logits(queries, keys, head_set, dense, dims):
+    """The heads' logits [N, sum(dims)] materialised the reference's way (baseline_policy.py:58-70,
+    :222-230): a zero embedding for the no-op appended to every key set, one batched mat-vec per
+    pointer head, the dense heads' logits in between. Arguments as for `heads.pointer_heads`."""
+    padded = [torch.cat([k, k.new_zeros(k.shape[0], 1, k.shape[2])], 1) for k in keys]
+    parts, p, d = [], 0, 0
+    for size, s in zip(dims, head_set):
+        if s < 0:
+            parts.append(dense[:, d:d + size])
+            d += size
+        else:
+            parts.append(torch.matmul(padded[s], queries[:, p].unsqueeze(-1)).squeeze(-1))
+            p += 1
+    return torch.cat(parts, 1)
+
+
+class PointerMaskedAgent(MaskedLinearAgent):
+    """The stand-in with the decoder shape of the reference's policies (baseline_policy.py:58-70,
+    :222-230; SPEC.md §18): the eight heads that choose an entity, an inventory slot or a market
+    listing are pointer heads. Each takes its logits as the dot products of a query, a
+    `Linear(hidden, hidden)` of the hidden row, with the row's candidate embeddings, a
+    `Linear(cols, hidden)` over the row's Entity [100, 31], Inventory [12, 16] or Market [1024, 16]
+    section (squashed by tanh(x / 64), the query scaled by 1 / sqrt(hidden): the logits stay within
+    a few units), plus a zero logit for the no-op entry. The four other heads keep a `Linear(hidden, n)`.
+
+    `fused_pointer=True` runs all twelve heads as one `heads.pointer_heads` call (philox draws,
+    `draws` and int32 actions as with `fused_heads`); otherwise the logits are materialised the
+    reference's way, `cat` of a zero row and `matmul`, and go through the parent's path.
+
+    The market keys alone are 256 KB per row at hidden 64: this stand-in is for the loop's small
+    shapes, not for the 131,072 rows of C4."""
+
+    SETS = (("Entity", ("Attack.Target", "Give.Target", "GiveGold.Target")),
+            ("Inventory", ("Destroy.InventoryItem", "Give.InventoryItem", "Sell.InventoryItem", "Use.InventoryItem")),
+            ("Market", ("Buy.MarketItem",)))
+
+    def __init__(self, task_dim: int = 2048, hidden: int = 64, fused_heads: bool = False, seed: int = 0,
+                 fused_pointer: bool = False):
+        super().__init__(task_dim, hidden, fused_heads, seed)
+        del self.actor  # every head has its own layer below
+        self.fused_pointer = bool(fused_pointer)
+        lay = layout.flat_layout(task_dim)
+        self.sections = [(lay[name].offset, *lay[name].shape) for name, _ in self.SETS]
+        self.head_set = [-1] * len(self.dims)
+        for s, (_, names) in enumerate(self.SETS):
+            for name in names:
+                self.head_set[layout.HEAD[name]] = s
+        self.key_encoders = nn.ModuleList(nn.Linear(cols, hidden) for _, _, cols in self.sections)
+        self.queries = nn.ModuleList(nn.Linear(hidden, hidden) for s in self.head_set if s >= 0)
+        self.dense = nn.ModuleList(nn.Linear(hidden, n) for n, s in zip(self.dims, self.head_set) if s < 0)
+        self.query_scale = 1.0 / math.sqrt(hidden)
+
+    def heads(self, h: torch.Tensor, obs: torch.Tensor, action: torch.Tensor | None = None):
+        n = obs.shape[0]
+        keys = [enc(torch.tanh(obs[:, o:o + rows * cols].reshape(n, rows, cols) / 64.0))
+                for enc, (o, rows, cols) in zip(self.key_encoders, self.sections)]
+        queries = torch.stack([q(h) for q in self.queries], 1) * self.query_scale
+        dense = torch.cat([d(h) for d in self.dense], 1)
+        if self.fused_pointer:
+            from .heads import pointer_heads
+
+            acts, logp, ent = pointer_heads(queries, keys, self.head_set, dense, obs, self.dims, action,
+                                            seed=self.seed, offset=self.draws)
+            if action is None:
+                self.draws += 1
+            return acts, logp, ent, self.value(h)
+        return self.masked(pointer_logits(queries, keys, self.head_set, dense, self.dims), h, obs, action)
 
 
 class RecurrentMaskedAgent(MaskedLinearAgent):
