@@ -106,6 +106,43 @@ NMH_API int nmh_pointer_backward(const NmhHeads* hd, const NmhPointer* pt, int32
                                  const float* g_logprob, const float* g_entropy, float* g_dense,
                                  int64_t g_dense_stride, float* g_queries, float* const* g_keys, void* stream);
 
+/* ---- Tile encoder (SPEC.md §19): the embedding, the first 3x3 convolution and the ReLU of the
+ * reference's TileEncoder (baseline_policy.py:95-107) as one lookup into a table folded from the
+ * two layers' weights, table[f][v][k][o] = sum_e W1[o][f*32 + e][ky][kx] E[f*256 + v][e], k = ky*3 + kx.
+ * The shape is the start-kit policy's. */
+#define NMH_TILE_TILES 225    /* 15 x 15 tiles per row, in order t = y*15 + x */
+#define NMH_TILE_FEATURES 3   /* (row, col, material) per tile */
+#define NMH_TILE_VALUES 256   /* embedding rows per feature */
+#define NMH_TILE_TAPS 9       /* 3 x 3 */
+#define NMH_TILE_CHANNELS 32  /* output channels */
+#define NMH_TILE_OUT 169      /* 13 x 13 output positions per channel */
+#define NMH_TILE_FWD_ROWS 4   /* rows per workgroup of the forward kernel */
+#define NMH_TILE_MAX_CHUNKS 64
+
+#define NMH_TILE_F32 0 /* float32 Tile section (the flat obs row) */
+#define NMH_TILE_I16 1 /* int16 Tile section (the native obs row) */
+
+/* tile: row r's Tile section, 675 entries (row, col, material) x 225 read in place at
+ * tile + r * tile_stride elements of the kind's type; tile_stride >= 675, rows need no alignment
+ * beyond their element's, and the input is never written. idx[t][f] = clamp(trunc(v), 0, 255) with
+ * v = (tile[t][f] - tile[112][f]) + 7 for f < 2 (float32: two roundings; NaN gives 0) and
+ * v = tile[t][2] for the material.
+ * out [n_rows, 32, 13, 13] = max(0, bias[o] + sum over ky, kx, f in that order of
+ * table[f][idx[(y+ky)*15 + x+kx][f]][ky*3+kx][o]), float32 without contraction.
+ * table [3, 256, 9, 32] and bias [32] are 16-byte aligned. idx_out: NULL, or uint8 [n_rows, 225, 3]
+ * that receives idx (what nmh_tile_backward reads). */
+NMH_API int nmh_tile_forward(int32_t n_rows, const void* tile, int64_t tile_stride, int32_t tile_kind,
+                             const float* table, const float* bias, float* out, uint8_t* idx_out, void* stream);
+
+/* The gradient with respect to table and bias, given idx and out as nmh_tile_forward stored them
+ * and g_out like out (out and g_out contiguous and 16-byte aligned). Chunk c of n_chunks
+ * (1..NMH_TILE_MAX_CHUNKS) covers rows [c R, min(n_rows, (c+1) R)), R = ceil(n_rows / n_chunks);
+ * g_table_parts [n_chunks, 3, 256, 9, 32] and g_bias_parts [n_chunks, 32] receive each chunk's
+ * sums, every entry written (an empty chunk's are zeros), and the caller adds the chunks. No
+ * atomics: the same bits on every run for a given (n_rows, n_chunks). */
+NMH_API int nmh_tile_backward(int32_t n_rows, const uint8_t* idx, const float* out, const float* g_out,
+                              int32_t n_chunks, float* g_table_parts, float* g_bias_parts, void* stream);
+
 NMH_API const char* nmh_last_error(void);
 /* "src=<hash of the sources the library was compiled from> arch=gfx950 fp_contract=off" */
 NMH_API const char* nmh_build_info(void);

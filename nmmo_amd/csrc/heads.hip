@@ -609,6 +609,10 @@ int check_pointer(const char* fn, const NmhHeads* hd, const NmhPointer* pt, int3
 
 }  // namespace
 
+// For the library's other translation unit (tile_enc.hip), whose copy of host_api.h's g_err is not
+// the one nmh_last_error() reads. Hidden visibility: not an export.
+int heads_record_error(int code, const char* msg) { return fail(code, "%s", msg); }
+
 extern "C" {
 
 const char* nmh_last_error(void) { return g_err.c_str(); }

@@ -22,8 +22,8 @@ import os
 from . import _loader, build
 
 LIB_PATH = os.environ.get("NMMO_HEADS_LIB", build.lib_path("heads"))
-SYMBOLS = ["nmh_forward", "nmh_backward", "nmh_pointer_forward", "nmh_pointer_backward", "nmh_last_error",
-           "nmh_build_info"]
+SYMBOLS = ["nmh_forward", "nmh_backward", "nmh_pointer_forward", "nmh_pointer_backward", "nmh_tile_forward",
+           "nmh_tile_backward", "nmh_last_error", "nmh_build_info"]
 MAX_HEADS, MAX_DIM = 16, 2048
 MAX_SETS, MAX_KEY_DIM = 4, 256
 MASK_F32, MASK_U8 = 0, 1
@@ -53,6 +53,8 @@ def declare(L):
                                        kp, vp]
     L.nmh_forward.argtypes = [hp, i32, vp, i64, vp, i64, i32, vp, u64, u64, ctypes.c_uint32, vp, vp, vp, vp, vp, vp]
     L.nmh_backward.argtypes = [hp, i32, vp, i64, vp, i64, i32, vp, vp, vp, vp, vp, vp, i64, vp]
+    L.nmh_tile_forward.argtypes = [i32, vp, i64, i32, vp, vp, vp, vp, vp]  # nmmo_amd/tile.py
+    L.nmh_tile_backward.argtypes = [i32, vp, vp, vp, i32, vp, vp, vp]
 
 
 def lib():

@@ -16,6 +16,8 @@ The policy networks themselves are out of scope (consumers of the
 by the obs ActionTargets (baseline_policy.py:245-262) — so the loop can be exercised and timed.
 `PointerMaskedAgent` is the same stand-in with the reference decoders' pointer heads
 (baseline_policy.py:222-230; SPEC.md §18).
+`TileMaskedAgent` is the same stand-in behind the reference's tile encoder
+(baseline_policy.py:85-112; SPEC.md §19).
 `RecurrentMaskedAgent` is the same stand-in with an LSTM between encoder and heads and the
 reference's recurrent convention, `agent(obs, state, action=None) -> (..., state)`: for an agent
 with an `.lstm` attribute the loop carries one LSTM state per agent slot through `evaluate()` and
@@ -190,6 +192,27 @@ class PointerMaskedAgent(MaskedLinearAgent):
                 self.draws += 1
             return acts, logp, ent, self.value(h)
         return self.masked(pointer_logits(queries, keys, self.head_set, dense, self.dims), h, obs, action)
+
+
+class TileMaskedAgent(MaskedLinearAgent):
+    """The stand-in with the observation encoder every reference policy starts with: the
+    reference's `TileEncoder` (baseline_policy.py:85-112: 225 x 3 embeddings, two convolutions, a
+    linear layer; `nmmo_amd/tile.py`) over the row's Tile section, then the tick and one hidden
+    layer as in the parent. `fused_tile=True` runs the embedding, the first convolution and its
+    ReLU as one `tile.tile_conv1` call (the HIP kernels of SPEC.md §19), reading the obs rows in
+    place. The call convention is the parent's."""
+
+    def __init__(self, task_dim: int = 2048, hidden: int = 64, fused_heads: bool = False, seed: int = 0,
+                 fused_tile: bool = False):
+        super().__init__(task_dim, hidden, fused_heads, seed)
+        from .tile import TileEncoder
+
+        self.tile_encoder = TileEncoder(hidden, fused=fused_tile)
+        self.encoder = nn.Sequential(nn.Linear(hidden + 1, hidden), nn.ReLU())
+
+    def forward(self, obs: torch.Tensor, action: torch.Tensor | None = None):
+        tick = obs[:, self.o_tick:self.o_tick + 1] / 1024.0
+        return self.heads(self.encoder(torch.cat([self.tile_encoder(obs, self.o_tile), tick], 1)), obs, action)
 
 
 class RecurrentMaskedAgent(MaskedLinearAgent):
