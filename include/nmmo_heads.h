@@ -143,6 +143,56 @@ NMH_API int nmh_tile_forward(int32_t n_rows, const void* tile, int64_t tile_stri
 NMH_API int nmh_tile_backward(int32_t n_rows, const uint8_t* idx, const float* out, const float* g_out,
                               int32_t n_chunks, float* g_table_parts, float* g_bias_parts, void* stream);
 
+/* ---- Item encoder (SPEC.md §20): the reference's ItemEncoder (baseline_policy.py:148-170) is a
+ * linear layer over a fixed 32-feature function x of an item's 16 columns, so its mean pool needs
+ * only the sum of x over a set, and a pointer logit q . fc(x_j) = (W^T q) . x_j + q . b needs only
+ * candidate j's own columns. No embedding tensor is made.
+ * x[i] = (i == t), i < 18, t = clamp(trunc(col 1), 0, 17); x[18 + i] = (i == e), i < 2,
+ * e = clamp(trunc(col 14), 0, 1); NaN gives class 0; x[20 + k] = col cont[k] * 0.01f, one float32
+ * product, cont = 3, 4, ..., 13, 15. */
+#define NMH_ITEM_COLS 16
+#define NMH_ITEM_FEATURES 32
+#define NMH_ITEM_TYPES 18
+#define NMH_ITEM_QUERY 36      /* floats per projected query: 32 weights, the constant, 3 pads */
+#define NMH_ITEM_MAX_ROWS 1024 /* items per set */
+#define NMH_ITEM_MAX_HEADS 4   /* heads over one set per call */
+
+#define NMH_ITEM_F32 0 /* float32 item columns (the flat obs row) */
+#define NMH_ITEM_I16 1 /* int16 item columns (the native obs), converted exactly */
+
+/* items: set m's R x 16 item columns read in place at items + m * item_stride elements of the kind's
+ * type (item_stride >= 16 R; rows need no alignment beyond their element's; never written).
+ * features [n_sets, R, 32] and sums [n_sets, 32]: either may be NULL, not both.
+ * sums[f] = the number of items of the class, f < 20 (exact); sums[20 + k] = (sum over the set's items of
+ * col cont[k], in one fixed order) * 0.01f. 1 <= R = set_rows <= NMH_ITEM_MAX_ROWS; n_sets == 0 is a no-op. */
+NMH_API int nmh_item_features(int32_t n_sets, const void* items, int64_t item_stride, int32_t item_kind,
+                              int32_t set_rows, float* features, float* sums, void* stream);
+
+typedef struct NmhItemHeads { /* 1..NMH_ITEM_MAX_HEADS heads over one item set */
+  int32_t n_heads;
+  int32_t mask_off[NMH_ITEM_MAX_HEADS]; /* head h's first of set_rows + 1 entries in a mask row */
+  int32_t out_off[NMH_ITEM_MAX_HEADS];  /* ... and in an out / g_out row */
+} NmhItemHeads;
+
+/* Obs row r reads item set r / share (share >= 1: 1 for flat rows, P for the native per-env Market).
+ * pq [n_rows, n_heads, 36], 16-byte aligned. out [n_rows, out_stride]. Mask as in nmh_forward; both
+ * strides cover the furthest head's set_rows + 1 entries.
+ * out[r][out_off[h] + j], j < R legal: v = pq[32] + pq[t]; v += pq[18 + e]; v = fmaf(pq[20 + k], x[20 + k], v),
+ * k = 0..11. Illegal j and the no-op j = R: 0.0f. All R + 1 entries are written, nothing else is, and
+ * the items of illegal candidates are never read. n_rows == 0 is a no-op. */
+NMH_API int nmh_item_logits(const NmhItemHeads* ih, int32_t n_rows, const void* items, int64_t item_stride,
+                            int32_t item_kind, int32_t set_rows, int32_t share, const void* mask,
+                            int64_t mask_stride, int32_t mask_kind, const float* pq, float* out,
+                            int64_t out_stride, void* stream);
+
+/* g_pq [n_rows, n_heads, 36]: g_pq[f] = fmaf(g_out[j], (x_j, 1)[f], .) over the legal j < R in
+ * ascending order, f < 33; the three pads are written as 0. g_out [n_rows, g_stride] like out; its
+ * entries of illegal candidates and of the no-op are not read. No atomics: the same bits on every run. */
+NMH_API int nmh_item_logits_backward(const NmhItemHeads* ih, int32_t n_rows, const void* items, int64_t item_stride,
+                                     int32_t item_kind, int32_t set_rows, int32_t share, const void* mask,
+                                     int64_t mask_stride, int32_t mask_kind, const float* g_out, int64_t g_stride,
+                                     float* g_pq, void* stream);
+
 NMH_API const char* nmh_last_error(void);
 /* "src=<hash of the sources the library was compiled from> arch=gfx950 fp_contract=off" */
 NMH_API const char* nmh_build_info(void);

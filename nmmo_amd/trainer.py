@@ -18,6 +18,9 @@ by the obs ActionTargets (baseline_policy.py:245-262) — so the loop can be exe
 (baseline_policy.py:222-230; SPEC.md §18).
 `TileMaskedAgent` is the same stand-in behind the reference's tile encoder
 (baseline_policy.py:85-112; SPEC.md §19).
+`ItemMaskedAgent` is the same stand-in with the reference's item path: the item encoder over
+Inventory and Market, their pooled embeddings and the five item pointer heads
+(baseline_policy.py:47-51, 148-190; SPEC.md §20).
 `RecurrentMaskedAgent` is the same stand-in with an LSTM between encoder and heads and the
 reference's recurrent convention, `agent(obs, state, action=None) -> (..., state)`: for an agent
 with an `.lstm` attribute the loop carries one LSTM state per agent slot through `evaluate()` and
@@ -213,6 +216,98 @@ class TileMaskedAgent(MaskedLinearAgent):
     def forward(self, obs: torch.Tensor, action: torch.Tensor | None = None):
         tick = obs[:, self.o_tick:self.o_tick + 1] / 1024.0
         return self.heads(self.encoder(torch.cat([self.tile_encoder(obs, self.o_tile), tick], 1)), obs, action)
+
+
+class ItemMaskedAgent(MaskedLinearAgent):
+    """The stand-in with the reference's item path (baseline_policy.py:47-51, 148-190, 222-230;
+    `nmmo_amd/item.py`, SPEC.md §20): one `ItemEncoder` over the row's Inventory [12, 16] and Market
+    [1024, 16] sections. The hidden row is the parent's (materials and tick) plus a
+    `Linear(12 hidden, hidden)` over the inventory embeddings (`InventoryEncoder`) plus a
+    `Linear(hidden, hidden)` over the pooled market embedding (`MarketEncoder`). The four
+    `*.InventoryItem` heads and `Buy.MarketItem` are pointer heads over the item embeddings, each
+    with a `Linear(hidden, hidden)` query scaled by 1 / sqrt(hidden) as in `PointerMaskedAgent`;
+    the other seven heads keep a `Linear(hidden, n)`. Either way the [N, 1586] logits go through the
+    parent's `masked`, so `fused_heads` works with both.
+
+    `fused_item=False` materialises the embeddings, pads the zero row and uses `matmul`, the
+    reference's way: 256 KB of market embeddings per row at hidden 64. `fused_item=True` makes one
+    `item.item_logits` call per set and one `item.item_sums` call, reading the obs rows in place,
+    and holds no [N, 1024, .] tensor. The call convention is the parent's."""
+
+    SETS = (("Inventory", ("Destroy.InventoryItem", "Give.InventoryItem", "Sell.InventoryItem", "Use.InventoryItem")),
+            ("Market", ("Buy.MarketItem",)))
+
+    def __init__(self, task_dim: int = 2048, hidden: int = 64, fused_heads: bool = False, seed: int = 0,
+                 fused_item: bool = False):
+        super().__init__(task_dim, hidden, fused_heads, seed)
+        from .item import ItemEncoder
+
+        del self.actor  # every head has its own layer below
+        lay = layout.flat_layout(task_dim)
+        self.sections = [(lay[name].offset, *lay[name].shape) for name, _ in self.SETS]
+        self.set_heads = [[layout.HEAD[name] for name in names] for _, names in self.SETS]
+        pointer = sorted(k for ks in self.set_heads for k in ks)
+        self.query_of = {k: p for p, k in enumerate(pointer)}  # head -> its row of `queries`
+        self.item_encoder = ItemEncoder(hidden, fused=fused_item)
+        self.inventory = nn.Linear(layout.INVENTORY_N_OBS * hidden, hidden)
+        self.market = nn.Linear(hidden, hidden)
+        self.queries = nn.ModuleList(nn.Linear(hidden, hidden) for _ in pointer)
+        self.dense = nn.ModuleList(nn.Linear(hidden, n) for k, n in enumerate(self.dims) if k not in self.query_of)
+        self.query_scale = 1.0 / math.sqrt(hidden)
+
+    def item_sets(self, obs: torch.Tensor):
+        """The rows' Inventory and Market sections, as views of `obs`."""
+        return [obs[:, o:o + rows * cols] for o, rows, cols in self.sections]
+
+    def hidden(self, obs: torch.Tensor):
+        """(the hidden rows, the inventory embeddings [N, 12, H], the market embeddings [N, 1024, H]
+        or None on the fused path)."""
+        mat = obs[:, self.o_tile + 2:self.o_tile + 3 * layout.TILE_ROWS:3] / 16.0
+        tick = obs[:, self.o_tick:self.o_tick + 1] / 1024.0
+        inv, mk = self.item_sets(obs)
+        enc = self.item_encoder
+        inv_emb = enc.embed(inv)
+        if enc.fused:
+            mk_emb, market = None, self.market(enc.pooled(mk))
+        else:
+            mk_emb = enc.embed(mk)
+            market = self.market(mk_emb).mean(-2)
+        return self.encoder(torch.cat([mat, tick], 1)) + self.inventory(inv_emb.flatten(1)) + market, inv_emb, mk_emb
+
+    def forward(self, obs: torch.Tensor, action: torch.Tensor | None = None):
+        h, inv_emb, mk_emb = self.hidden(obs)
+        return self.masked(self.logits(h, obs, inv_emb, mk_emb), h, obs, action)
+
+    def heads(self, h: torch.Tensor, obs: torch.Tensor, action: torch.Tensor | None = None):
+        inv, mk = self.item_sets(obs)
+        enc = self.item_encoder
+        embs = (None, None) if enc.fused else (enc.embed(inv), enc.embed(mk))
+        return self.masked(self.logits(h, obs, *embs), h, obs, action)
+
+    def logits(self, h, obs, inv_emb=None, mk_emb=None):
+        """The twelve heads' logits [N, 1586] in head order. The unfused path takes the item
+        embeddings; the fused path reads the rows (its illegal and no-op entries are 0)."""
+        queries = torch.stack([q(h) for q in self.queries], 1) * self.query_scale  # [N, 5, H]
+        parts = [None] * len(self.dims)
+        dense = iter(self.dense)
+        for k in range(len(self.dims)):
+            if k not in self.query_of:
+                parts[k] = next(dense)(h)
+        if self.item_encoder.fused:
+            from .item import item_logits
+
+            pq = self.item_encoder.pointer_query(queries)
+            for items, ks in zip(self.item_sets(obs), self.set_heads):
+                rows = self.dims[ks[0]]
+                lg = item_logits(items, pq[:, [self.query_of[k] for k in ks]], obs, [self.mask_off[k] for k in ks])
+                for i, k in enumerate(ks):
+                    parts[k] = lg[:, i * rows:(i + 1) * rows]
+        else:
+            for emb, ks in zip((inv_emb, mk_emb), self.set_heads):
+                padded = torch.cat([emb, emb.new_zeros(emb.shape[0], 1, emb.shape[2])], 1)
+                for k in ks:
+                    parts[k] = torch.matmul(padded, queries[:, self.query_of[k]].unsqueeze(-1)).squeeze(-1)
+        return torch.cat(parts, 1)
 
 
 class RecurrentMaskedAgent(MaskedLinearAgent):
