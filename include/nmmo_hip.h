@@ -502,7 +502,9 @@ NMMO_API int nmmo_scripted_actions(NmmoHandle* h, uint64_t policy_seed, int32_t*
 /* State blob: per env, [NMMO_NE int32 env fields][NF*slots int16 entity table]
  * [slots int16 free-row ring][MAP_TILES u8 material][player_n*12 x 2 u32 items]
  * [12*player_n int16 item-row ring][player_n int32 task index][player_n NmmoTaskState];
- * envs concatenated. Synchronous. */
+ * envs concatenated. Synchronous. With the wrapper layer on, nmmo_set_state also re-initialises it
+ * as nmmo_set_wrapper does (SPEC §13 Reset): wrapper states and bitsets cleared, info.done = 0, each
+ * env's cursor at the blob's E_EVENT_COUNT; the dropped-row counter is kept. */
 NMMO_API int nmmo_get_state(NmmoHandle* h, void* host_buf, size_t nbytes);
 NMMO_API int nmmo_set_state(NmmoHandle* h, const void* host_buf, size_t nbytes);
 /* The generated map bank: host u8 [map_n][MAP_TILES]. Synchronous. */
@@ -551,6 +553,13 @@ NMMO_API int nmmo_inject_fault(NmmoHandle* h, int32_t fault);
  * their count into *n_rows (retained = min(E_EVENT_COUNT, event_cap)). Synchronous. */
 NMMO_API int nmmo_get_events(NmmoHandle* h, int32_t env, int32_t* host_rows, int32_t max_rows,
                              int32_t* n_rows);
+/* Test hook: appends host_rows [n_rows][NMMO_EVENT_COLS] to env `env`'s ring exactly where the
+ * tick would (row i at ring row (E_EVENT_COUNT + i) % event_cap, every column as given) and adds
+ * n_rows to E_EVENT_COUNT; with n_rows > event_cap the last event_cap rows survive, as in the
+ * tick. The wrapper layer walks them with the rows of the env's next step. NMMO_E_INVALID without
+ * an event log (event_cap == 0), on an env outside [0, n_envs), n_rows < 0 or NULL rows.
+ * Synchronous. */
+NMMO_API int nmmo_inject_events(NmmoHandle* h, int32_t env, const int32_t* host_rows, int32_t n_rows);
 
 /* ---- GPU-resident experience storage ----
  * The trainer-side buffers of the reference's clean_pufferl kept in HBM (the reference keeps

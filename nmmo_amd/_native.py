@@ -26,7 +26,7 @@ SYMBOLS = [
     "nmmo_obs_bind", "nmmo_obs_invalidate_envs", "nmmo_exp_scratch_ints_many", "nmmo_set_step_records",
     "nmmo_wire_check_many", "nmmo_exp_store_records_checked", "nmmo_sizes_row",
     "nmmo_obs_invalidate_sections", "nmmo_p2p_load", "nmmo_p2p_unique_id", "nmmo_p2p_init", "nmmo_p2p_group",
-    "nmmo_p2p_destroy",
+    "nmmo_p2p_destroy", "nmmo_inject_events",
 ]
 
 
@@ -71,6 +71,7 @@ def declare(L):
     L.nmmo_read_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i32)]
     L.nmmo_set_counters.argtypes = [vp, vp]
     L.nmmo_get_events.argtypes = [vp, i32, vp, i32, ctypes.POINTER(i32)]
+    L.nmmo_inject_events.argtypes = [vp, i32, vp, i32]
     L.nmmo_set_tasks.argtypes = [vp, vp, i32, vp, vp]
     L.nmmo_set_task_weights.argtypes = [vp, vp, i32]
     L.nmmo_set_wrapper.argtypes = [vp, ctypes.POINTER(abi.NmmoWrapperConfig), vp]

@@ -1126,6 +1126,9 @@ int nmmo_set_state(NmmoHandle* h, const void* host_buf, size_t nbytes) {
   HIP_TRY(hipMemcpy(h->d_assign, assign.data(), assign.size() * 4, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(h->d_tstate, tstate.data(), tstate.size() * sizeof(NmmoTaskState), hipMemcpyHostToDevice));
   HIP_TRY(launch_rebuild_dep(h->st, nullptr));
+  // the wrapper layer starts over on the new state (SPEC §13 Reset), as nmmo_set_wrapper leaves it:
+  // a cursor above the blob's E_EVENT_COUNT would hide every row up to the old count
+  if (h->wrap_on) HIP_TRY(launch_wrap(wrap_params(h, nullptr, nullptr, nullptr, nullptr, nullptr), 1, nullptr));
   HIP_TRY(hipDeviceSynchronize());
   h->native_fresh = false;  // the last native obs no longer describes the state (nmmo_wire_pack)
   return NMMO_OK;
@@ -1299,6 +1302,35 @@ int nmmo_get_events(NmmoHandle* h, int32_t env, int32_t* host_rows, int32_t max_
     HIP_TRY(hipMemcpy(host_rows + (size_t)n1 * NMMO_EVENT_COLS, ring, (size_t)(n - n1) * NMMO_EVENT_COLS * 4,
                       hipMemcpyDeviceToHost));
   *n_rows = n;
+  return NMMO_OK;
+}
+
+int nmmo_inject_events(NmmoHandle* h, int32_t env, const int32_t* host_rows, int32_t n_rows) {
+  if (!h || !host_rows) return fail(NMMO_E_INVALID, "null argument");
+  const int cap = h->cfg.event_cap;
+  if (cap <= 0) return fail(NMMO_E_INVALID, "nmmo_inject_events needs the event log (event_cap > 0)");
+  if (env < 0 || env >= h->st.n_envs) return fail(NMMO_E_INVALID, "env %d out of range", env);
+  if (n_rows < 0) return fail(NMMO_E_INVALID, "n_rows %d < 0", n_rows);
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipDeviceSynchronize());
+  int32_t* d_cnt = h->d_env + (size_t)env * NMMO_NE + E_EVENT_COUNT;
+  int32_t cnt = 0;
+  HIP_TRY(hipMemcpy(&cnt, d_cnt, 4, hipMemcpyDeviceToHost));
+  if (cnt < 0 || cnt > INT32_MAX - n_rows) return fail(NMMO_E_INVALID, "event count %d + %d rows overflows", cnt, n_rows);
+  int32_t* ring = h->d_events + (size_t)env * cap * NMMO_EVENT_COLS;
+  // only the last event_cap rows survive; they occupy consecutive ring rows (one wrap at the most)
+  const int skip = n_rows > cap ? n_rows - cap : 0, n = n_rows - skip;
+  const int first = (int)(((int64_t)cnt + skip) % cap);
+  const int n1 = n < cap - first ? n : cap - first;
+  const int32_t* src = host_rows + (size_t)skip * NMMO_EVENT_COLS;
+  if (n1 > 0)
+    HIP_TRY(hipMemcpy(ring + (size_t)first * NMMO_EVENT_COLS, src, (size_t)n1 * NMMO_EVENT_COLS * 4,
+                      hipMemcpyHostToDevice));
+  if (n > n1)
+    HIP_TRY(hipMemcpy(ring, src + (size_t)n1 * NMMO_EVENT_COLS, (size_t)(n - n1) * NMMO_EVENT_COLS * 4,
+                      hipMemcpyHostToDevice));
+  cnt += n_rows;
+  HIP_TRY(hipMemcpy(d_cnt, &cnt, 4, hipMemcpyHostToDevice));
   return NMMO_OK;
 }
 

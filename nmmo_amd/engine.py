@@ -339,6 +339,10 @@ class NmmoEngine:
         return buf
 
     def set_state(self, buf: np.ndarray):
+        """Replace every env's state with the blob (nmmo_set_state). With the wrapper layer on it
+        starts over as set_wrapper leaves it (SPEC §13 Reset): wrapper states and `experienced`
+        bitsets cleared, info.done = 0, each env's event cursor at the blob's event count; the
+        dropped-row counter is kept."""
         buf = np.ascontiguousarray(buf, dtype=np.uint8)
         check(lib().nmmo_set_state(self.h, buf.ctypes.data_as(ctypes.c_void_p), buf.nbytes),
               "nmmo_set_state")
@@ -389,6 +393,15 @@ class NmmoEngine:
         check(lib().nmmo_get_events(self.h, env, buf.ctypes.data_as(ctypes.c_void_p), m, ctypes.byref(n)),
               "nmmo_get_events")
         return buf[:n.value].copy()
+
+    def inject_events(self, env: int, rows):
+        """Test hook (nmmo_inject_events): append int32 rows [n, 9] (SPEC §11 columns, as given)
+        to `env`'s event ring where the tick would and add n to its event count; the wrapper
+        layer walks them with the rows of the env's next step. Synchronous."""
+        rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1, abi.EVENT_COLS)
+        buf = rows if rows.size else np.zeros((1, abi.EVENT_COLS), np.int32)
+        check(lib().nmmo_inject_events(self.h, int(env), buf.ctypes.data_as(ctypes.c_void_p), rows.shape[0]),
+              "nmmo_inject_events")
 
     def map_bank(self) -> np.ndarray:
         buf = np.zeros((self.config.MAP_N, abi.MAP_SIZE, abi.MAP_SIZE), np.uint8)

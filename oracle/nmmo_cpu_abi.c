@@ -33,6 +33,7 @@ int oracle_set_state(void* h, const void* buf, size_t nbytes);
 int oracle_set_tasks(void* h, const NmmoTask* tasks, int n_tasks, const uint16_t* emb, const int32_t* assign);
 int oracle_set_task_weights(void* h, const double* w, int n_tasks);
 int oracle_get_events(void* h, int env, int32_t* rows, int max_rows, int* n_rows);
+int oracle_inject_events(void* h, int env, const int32_t* rows, int n_rows);
 int oracle_set_map_bank(void* h, const uint8_t* buf, size_t nbytes);
 int oracle_get_map_bank(void* h, uint8_t* buf, size_t nbytes);
 int oracle_obs_elems(int task_dim);
@@ -241,6 +242,13 @@ NMMO_API int nmmo_get_events(NmmoHandle* h, int32_t env, int32_t* host_rows, int
   if (!h || !n_rows) return fail(NMMO_E_INVALID, "null argument");
   if (env < 0 || env >= h->n_envs) return fail(NMMO_E_INVALID, "env %d out of range", env);
   return oracle_get_events(h->o, env, host_rows, max_rows, n_rows);
+}
+NMMO_API int nmmo_inject_events(NmmoHandle* h, int32_t env, const int32_t* host_rows, int32_t n_rows) {
+  if (!h || !host_rows) return fail(NMMO_E_INVALID, "null argument");
+  if (h->cfg.event_cap <= 0) return fail(NMMO_E_INVALID, "nmmo_inject_events needs the event log (event_cap > 0)");
+  if (env < 0 || env >= h->n_envs) return fail(NMMO_E_INVALID, "env %d out of range", env);
+  if (n_rows < 0) return fail(NMMO_E_INVALID, "n_rows %d < 0", n_rows);
+  return oracle_inject_events(h->o, env, host_rows, n_rows);
 }
 
 /* ---- the device-only parts of the ABI ---- */

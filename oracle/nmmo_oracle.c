@@ -1579,6 +1579,20 @@ EXPORT int oracle_get_events(void* h, int env, int32_t* rows, int max_rows, int*
   return 0;
 }
 
+/* test hook (as nmmo_inject_events): rows appended to the env's ring as given, row i at ring index
+ * (event_count + i) mod event_cap, the count advanced by n_rows */
+EXPORT int oracle_inject_events(void* h, int env, const int32_t* rows, int n_rows) {
+  Oracle* o = (Oracle*)h;
+  const int cap = o->cfg.event_cap;
+  if (cap <= 0 || n_rows < 0) return NMMO_E_INVALID;
+  int32_t* E = ENV(o, env);
+  for (int i = 0; i < n_rows; i++)
+    memcpy(o->events + ((size_t)env * cap + (size_t)(((int64_t)E[E_EVENT_COUNT] + i) % cap)) * NMMO_EVENT_COLS,
+           rows + (size_t)i * NMMO_EVENT_COLS, NMMO_EVENT_COLS * 4);
+  E[E_EVENT_COUNT] += n_rows;
+  return 0;
+}
+
 EXPORT int oracle_set_map_bank(void* h, const uint8_t* buf, size_t nbytes) {
   Oracle* o = (Oracle*)h;
   if (nbytes != (size_t)o->cfg.map_n * NMMO_MAP_TILES) return NMMO_E_SIZE;

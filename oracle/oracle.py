@@ -48,6 +48,7 @@ def lib():
         L.oracle_set_task_weights.argtypes = [vp, vp, i32]
         L.oracle_write_obs.argtypes = [vp, i32, vp]
         L.oracle_get_events.argtypes = [vp, i32, vp, i32, ctypes.POINTER(i32)]
+        L.oracle_inject_events.argtypes = [vp, i32, vp, i32]
         L.oracle_set_tasks.argtypes = [vp, vp, i32, vp, vp]
         L.oracle_obs_elems.argtypes = [i32]
         L.oracle_flat_offsets.argtypes = [i32, vp]
@@ -166,6 +167,14 @@ class OracleEnvs:
         rc = lib().oracle_get_events(self.h, env, _p(buf), buf.shape[0], ctypes.byref(n))
         assert rc == 0, rc
         return buf[:n.value].copy()
+
+    def inject_events(self, env: int, rows):
+        """Test hook, as NmmoEngine.inject_events: int32 rows [n, 9] appended to `env`'s ring."""
+        rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1, abi.EVENT_COLS)
+        assert 0 <= env < self.n_envs
+        buf = rows if rows.size else np.zeros((1, abi.EVENT_COLS), np.int32)
+        rc = lib().oracle_inject_events(self.h, env, _p(buf), rows.shape[0])
+        assert rc == 0, rc
 
     def map_bank(self) -> np.ndarray:
         buf = np.zeros((self.config.MAP_N, abi.MAP_SIZE, abi.MAP_SIZE), np.uint8)

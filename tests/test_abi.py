@@ -167,6 +167,19 @@ def test_set_wrapper_rejects_bad_handles(native):
     assert native.nmmo_get_wrapper_state(None, None, None) == abi.NMMO_E_INVALID
 
 
+def test_inject_events_rejects_bad_arguments(native):
+    """The test hook nmmo_inject_events: a null handle or null rows are refused before anything is
+    touched (a bad env and a handle without an event log need a handle: tests/test_wrapper_cases.py
+    on the CPU stepper, tests/test_gpu_wrapper_states.py on the HIP library)."""
+    import numpy as np
+
+    rows = np.zeros((2, abi.EVENT_COLS), np.int32)
+    assert native.nmmo_inject_events(None, 0, rows.ctypes.data_as(ctypes.c_void_p), 2) == abi.NMMO_E_INVALID
+    assert b"null" in native.nmmo_last_error()
+    assert native.nmmo_inject_events(None, 0, None, 0) == abi.NMMO_E_INVALID
+    assert native.nmmo_inject_events(None, -1, None, -1) == abi.NMMO_E_INVALID
+
+
 def test_storage_structs_and_wire_layout_match_c_compiler():
     src = r"""
 #include <stdio.h>
