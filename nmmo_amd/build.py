@@ -44,6 +44,9 @@ LIBS = {
 SOURCES, HEADERS = LIBS["hip"].sources, LIBS["hip"].headers
 LIB_PATH = os.path.join(LIB_DIR, LIBS["hip"].file)
 STAMPS_PATH = os.path.join(LIB_DIR, "libnmmo_hip_stamps.so")
+# the product library's sources with -DNMMO_TEST_HOOKS: the same kernels plus read-only test hooks
+# (capi.hip nmmo_debug_obs_row_state), loaded through NMMO_LIB by the tests that need them
+HOOKS_PATH = os.path.join(LIB_DIR, "libnmmo_hip_hooks.so")
 FLAGS = [
     f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Werror",
     # no FMA contraction: hipcc contracts even __dadd_rn(__dmul_rn(..)) pairs, and the float /
@@ -84,18 +87,28 @@ def stale(name: str = "hip") -> bool:
         return ("src=" + source_hash(name)).encode() not in fh.read()
 
 
-def build_lib(name: str, force: bool = False, verbose: bool = False, stamps: bool = False) -> str:
+def _embeds(path: str, name: str) -> bool:
+    if not os.path.exists(path):
+        return False
+    with open(path, "rb") as fh:
+        return ("src=" + source_hash(name)).encode() in fh.read()
+
+
+def build_lib(name: str, force: bool = False, verbose: bool = False, stamps: bool = False, hooks: bool = False) -> str:
     """Library `name`; `stamps=True` builds the product library's diagnostic variant (phase clock
-    stamps, tools/stamps.py) to lib/libnmmo_hip_stamps.so instead."""
+    stamps, tools/stamps.py) to lib/libnmmo_hip_stamps.so instead, `hooks=True` its test-hook
+    variant to lib/libnmmo_hip_hooks.so (rebuilt when it does not embed the current source hash)."""
     row = LIBS[name]
-    if stamps and name != "hip":
-        raise ValueError("only the product library has a stamps variant")
-    out = STAMPS_PATH if stamps else lib_path(name)
-    if not force and not stamps and not stale(name):
+    if (stamps or hooks) and name != "hip":
+        raise ValueError("only the product library has variants")
+    out = STAMPS_PATH if stamps else HOOKS_PATH if hooks else lib_path(name)
+    if not force and hooks and _embeds(out, name):
+        return out
+    if not force and not stamps and not hooks and not stale(name):
         return out
     os.makedirs(LIB_DIR, exist_ok=True)
     tmp = out + ".tmp"
-    flags = [*FLAGS, *(["-DNMMO_STAMPS"] if stamps else []), f'-DNMMO_SRC_HASH="{source_hash(name)}"']
+    flags = [*FLAGS, *(["-DNMMO_STAMPS"] if stamps else []), *(["-DNMMO_TEST_HOOKS"] if hooks else []), f'-DNMMO_SRC_HASH="{source_hash(name)}"']
     # one hipcc per source in parallel (every kernel lives in its own translation unit), then link
     with tempfile.TemporaryDirectory(prefix="nmmo_build_") as d:
         objs = [os.path.join(d, f + ".o") for f in row.sources]
@@ -112,6 +125,7 @@ def build_lib(name: str, force: bool = False, verbose: bool = False, stamps: boo
 
 
 build = functools.partial(build_lib, "hip")
+build_hooks = functools.partial(build_lib, "hip", hooks=True)
 build_heads = functools.partial(build_lib, "heads")
 build_ppo = functools.partial(build_lib, "ppo")
 build_lstm = functools.partial(build_lib, "lstm")
@@ -120,3 +134,4 @@ build_lstm = functools.partial(build_lib, "lstm")
 if __name__ == "__main__":
     for lib_name in LIBS:
         print(build_lib(lib_name, force="--force" in sys.argv, verbose=True))
+    print(build_hooks(force="--force" in sys.argv, verbose=True))

@@ -336,6 +336,16 @@ __host__ __device__ constexpr uint64_t ao_req_lut() {  // type -> requirement la
   return m;
 }
 static_assert(T_RATION == 16 && T_POTION == 17, "requirement table: ration -> fishing, potion -> herbalism");
+// the lane (0..8 of the level lanes above) holding the requirement level of an item of `type`
+__device__ __forceinline__ int ao_req_lane(int type) {
+  return type < 16 ? (int)((ao_req_lut() >> (4 * type)) & 15u) : type == T_RATION ? 3 : type == T_POTION ? 4 : 8;
+}
+// Use.InventoryItem's entry for item word `it` (`have`: its slot is occupied) given its requirement's level
+__device__ __forceinline__ bool ao_usable(uint2 it, bool have, int req) {
+  const int type = it_type(it);
+  const bool eq = type >= T_HAT && type <= T_RUNES && it_equipped(it);  // equip_slot(type) >= 0
+  return have && !it_price(it) && (eq || it_level(it) <= req);
+}
 __device__ __forceinline__ uint64_t ao_usable_ballot(const int16_t* T, int Sp, int ti, uint2 it, bool have) {
   const int lane = ao_lane();
   int lv = 0;
@@ -344,11 +354,17 @@ __device__ __forceinline__ uint64_t ao_usable_ballot(const int16_t* T, int Sp, i
   } else if (lane == 8) {
     lv = max((int)T[F_MELEE_LEVEL * Sp + ti], max((int)T[F_RANGE_LEVEL * Sp + ti], (int)T[F_MAGE_LEVEL * Sp + ti]));
   }
-  const int type = it_type(it);
-  const int k = type < 16 ? (int)((ao_req_lut() >> (4 * type)) & 15u) : type == T_RATION ? 3 : type == T_POTION ? 4 : 8;
-  const int req = __shfl(lv, k);
-  const bool eq = type >= T_HAT && type <= T_RUNES && it_equipped(it);  // equip_slot(type) >= 0
-  return __ballot(have && !it_price(it) && (eq || it_level(it) <= req));
+  const int req = __shfl(lv, ao_req_lane(it_type(it)));
+  return __ballot(ao_usable(it, have, req));
+}
+
+// Visible row w (a packed word) seen by agent a at (r, c): tgt = its Attack.Target entry, st = another
+// player on the agent's tile (Give.Target / GiveGold.Target before the system and wrapper flags)
+__device__ __forceinline__ void ao_row_preds(uint32_t w, int a, int r, int c, bool combat, bool no_danger, bool& tgt,
+                                             bool& st) {
+  const int q = ao_slot(w);
+  tgt = combat && q != a && linf(r, c, ao_row(w), ao_col(w)) <= 3 && !ao_immune(w) && !(no_danger && ao_danger(w));
+  st = ao_player(w) && q != a && ao_row(w) == r && ao_col(w) == c;
 }
 
 // The 11 ActionTargets sections other than Buy.MarketItem as wave-uniform bit fields (SPEC §8,
@@ -378,11 +394,7 @@ __device__ __forceinline__ AoSections ao_sections(const ObsParams& p, const int1
     const int k = 64 * h + lane;
     bool tgt = false, st = false;
     if (k < g.nv) {
-      const uint32_t w = visw[k];
-      const int q = ao_slot(w);
-      tgt = combat && q != g.a && linf(g.r, g.c, ao_row(w), ao_col(w)) <= 3 && !ao_immune(w) &&
-            !(no_danger && ao_danger(w));
-      st = ao_player(w) && q != g.a && ao_row(w) == g.r && ao_col(w) == g.c;
+      ao_row_preds(visw[k], g.a, g.r, g.c, combat, no_danger, tgt, st);
     }
     x.s1[h] = __ballot(tgt);
     const uint64_t sb = __ballot(st);

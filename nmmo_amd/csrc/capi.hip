@@ -629,6 +629,27 @@ int nmmo_obs_invalidate(NmmoHandle* h, void* stream) {
   return NMMO_OK;
 }
 
+#ifdef NMMO_TEST_HOOKS
+// Test hook of the hook build only (build.py build_hooks: lib/libnmmo_hip_hooks.so, the same sources
+// with -DNMMO_TEST_HOOKS; the product library exports include/nmmo_hip.h and nothing else), read-only:
+// the flat obs row state copied to the host after the device has drained. tag: the bound buffer's
+// tag (a row's state is valid where zrow equals it); zrow, zst [n][P]; zext [n][P][kZext]
+// (ObsParams; NmmoEngine.obs_row_state).
+__attribute__((visibility("default"))) int nmmo_debug_obs_row_state(NmmoHandle* h, uint64_t* tag, uint64_t* zrow,
+                                                                     uint64_t* zst, uint64_t* zext) {
+  if (!h || !tag || !zrow || !zst || !zext) return fail(NMMO_E_INVALID, "null argument");
+  if (!h->d_zrow || !h->d_zext) return fail(NMMO_E_INVALID, "nmmo_debug_obs_row_state: flat obs layout only");
+  const size_t rows = (size_t)h->st.n_envs * h->st.P;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(zrow, h->d_zrow, rows * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(zst, h->d_zrow + rows, rows * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(zext, h->d_zext, rows * kZext * 8, hipMemcpyDeviceToHost));
+  *tag = h->zbuf ? h->ztag : 0;
+  return NMMO_OK;
+}
+#endif
+
 // the row-state tags of the listed envs' rows (zrow[e * P + a] = 0: nothing known about the row)
 __global__ void obs_forget_envs_kernel(uint64_t* zrow, const int32_t* ids, int n_ids, int n_envs, int P) {
   const int i = blockIdx.x, e = ids[i];

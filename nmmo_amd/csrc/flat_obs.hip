@@ -29,7 +29,9 @@ namespace nmmo {
 #ifndef NMMO_FO_ABL  // diagnostic ablation (timing attribution only, wrong rows): bit 1 masks, 2 Entity,
 #define NMMO_FO_ABL 0  // 4 Inventory, 8 Market, 16 Tile, 32 compaction, 64 the agent loop (prologue only),
 #endif                 // 128 everything (an empty launch), 256 rows aliased onto 128 per XCD (stores L2-resident)
-                       // (tools/debug/variants.py)
+                       // (tools/debug/variants.py; in the mirror variant bit 1 takes the mask pass out, and
+                       // with it the row-state write-back: every row is then written as one of unknown state;
+                       // bit 64 keeps the pass, prologue work, which then writes the state of rows nobody writes)
 #ifndef NMMO_FO_STAMPS  // diagnostic: s_memtime per section of every alive row (tools/debug/fo_stamps.py)
 #define NMMO_FO_STAMPS 0
 #endif
@@ -212,6 +214,190 @@ __device__ __forceinline__ void fo_tail_chunks(float* row, FoImg& g, const AoSec
     fo_put<kC>(row, g, m, aid, tick);
     fo_tail_chunks<kC + 1>(row, g, x, buy17, aid, tick);
   }
+}
+
+// The mirror variant's mask pass: the tracked chunks of all of a wave's agents built
+// once per wave, lane 10 j + slot = agent j's chunk `slot` (the layout the extended state is loaded
+// in), instead of once per row from wave-uniform values with 63 lanes idle.
+//  - the section fields over the visible rows and the inventory come from ballots whose lane
+//    16 j + k tests agent j's visible row / item k: four agents per ballot;
+//  - lane 10 j + slot assembles its chunk from agent j's fields (fo_chunk on per-lane values);
+//  - one compare with the loaded masks and one ballot give the changed bit of every (agent, chunk),
+//    one compare of the item words the Inventory sections' (bit 12 j + k);
+//  - the row state of the wave's agents in the realm goes out in a few wave-wide stores.
+// kFoPassRows: the visible rows a lane group holds. An agent that sees more (0.004 % of the bench
+// scenario's rows, tools/flat_window_counts.py) takes ao_sections' ballots over all of its rows, in
+// a loop of its own, for the three fields they feed. The listings need no bound: Buy's words 0 and
+// 15 (the tracked chunks' part) are one ballot per agent each, as in the per-row code.
+constexpr int kFoPassRows = 16;
+static_assert(kFoPassRows == 16 && kAoAgents / kAoWaves * kFoPassRows <= 64 && kInv <= kFoPassRows &&
+                  kFoGather <= kFoPassRows, "a 16-lane group per agent");
+constexpr int kFoBuyLane = 48;  // lane kFoBuyLane + j of FoPass::lo / hi: agent j's Buy word 0
+struct FoPass {
+  uint32_t lo, hi;  // lane 10 j + slot: agent j's new tracked mask; lanes 40 + j: as loaded (the Tile position)
+  uint64_t chg;     // bit 10 j + slot: the row does not hold that mask
+  uint64_t idiff;   // bit 12 j + k: the row's Inventory section was not written from item word k
+};
+template <int kSl>
+__device__ __forceinline__ void fo_pass_chunks(const AoSections& x, int sl, uint64_t& m) {
+  if constexpr (kSl < 10) {
+    constexpr int c = kSl < 2 ? kSl : kSl - 2 + kFoTail0;
+    static_assert(fo_slot(c) == kSl, "tracked chunk");
+    const uint64_t mc = fo_chunk<c>(x);
+    if (sl == kSl) m = mc;
+    fo_pass_chunks<kSl + 1>(x, sl, m);
+  }
+}
+// own: the workgroup's own agents' mirror rows; visw: the wave's agents' visible rows (agent j's at
+// j * kFoVisw); my_*: lane j = agent abase + kAoWaves * j (my_alive 0 past P); zvalid / zextv: the
+// agents' row state bits; img / pinv: the loaded extended state (zero where not valid)
+template <bool kWrap>
+__device__ __forceinline__ FoPass fo_mask_pass(const ObsParams& p, int e, int w, int abase, int nm, const int16_t* own,
+                                               const uint32_t* visw, const uint8_t* wsb, const uint2* ist,
+                                               const uint16_t* mpo, int my_nv, uint32_t my_rc, int my_prev, int my_alive,
+                                               int my_task, uint64_t zvalid, uint64_t zextv, uint2 img, uint2 pinv) {
+  constexpr int kPerWave = kAoAgents / kAoWaves;
+  const bool combat = (p.systems & NMMO_SYS_COMBAT) != 0;
+  const bool item = (p.systems & NMMO_SYS_ITEM) != 0;
+  const bool exch = item && (p.systems & NMMO_SYS_EXCHANGE) != 0;
+  const bool no_give = kWrap && (p.wflags & kWrapObsNoGive);
+  const bool no_danger = kWrap && (p.wflags & kWrapObsNoDangerous);
+  const int lane = lane_id(), P = p.P;
+  // lane 16 j + k: agent j's visible row k (1 AttackTarget; 5 GiveTarget / 7 GoldTarget's same-tile
+  // predicate) and its item k (3 Destroy / 4 GiveItem, 9 SellItem, 11 Use), as ao_sections
+  const int gj = lane >> 4, gk = lane & 15, ga = abase + kAoWaves * gj, gla = w + kAoWaves * gj;
+  const int grc = __shfl((int)my_rc, gj);
+  const int gr = (int16_t)(grc & 0xFFFF), gc = grc >> 16;
+  bool tgt = false, st = false;
+  if (gk < __shfl(my_nv, gj)) ao_row_preds(visw[gj * kFoVisw + gk], ga, gr, gc, combat, no_danger, tgt, st);
+  const uint64_t tb = __ballot(tgt), sb = __ballot(st);
+  const uint2 it = gk < kInv ? ist[gla * kInv + gk] : make_uint2(0u, 0u);
+  const uint64_t occ = __ballot(gk < kInv && it_type(it) != 0);
+  const bool have = gk < __builtin_ctz(~((uint32_t)(occ >> (16 * gj)) & 0xFFFFu));  // the occupied prefix
+  const uint64_t bfr = __ballot(have && !it_equipped(it) && !it_price(it));
+  const uint64_t bse = __ballot(have && !it_equipped(it));
+  uint64_t bus;
+  {  // ao_usable_ballot, the level lookup within the lane group
+    const int16_t* lvs = own + gla * kMirrorCols + F_MELEE_LEVEL;
+    int lv = 0;
+    if (gk < 8) lv = lvs[2 * gk];
+    else if (gk == 8) lv = max((int)lvs[0], max((int)lvs[F_RANGE_LEVEL - F_MELEE_LEVEL], (int)lvs[F_MAGE_LEVEL - F_MELEE_LEVEL]));
+    const int req = __shfl(lv, 16 * gj + ao_req_lane(it_type(it)));
+    bus = __ballot(ao_usable(it, have, req));
+  }
+  // lane 10 j + slot: agent j's fields (the lanes from 40 on compute agent 3's again, unused)
+  const int ja = min(lane / 10, kPerWave - 1), sl = lane - 10 * (lane / 10), la = w + kAoWaves * ja;
+  const uint64_t noop = 1ull << (kNObs - 64);
+  uint64_t t0 = (uint32_t)(tb >> (16 * ja)) & 0xFFFFu, t1 = 0ull, s0 = (uint32_t)(sb >> (16 * ja)) & 0xFFFFu, s1 = 0ull;
+#pragma unroll 1
+  for (int j = 0; j < kPerWave; j++) {  // an agent past the lane group: ao_sections' ballots over all of its rows
+    const int nv = __builtin_amdgcn_readlane(my_nv, j);
+    if (nv <= kFoPassRows) continue;
+    const int rcj = __builtin_amdgcn_readlane((int)my_rc, j), a = abase + kAoWaves * j;
+    const int r = (int16_t)(rcj & 0xFFFF), c = rcj >> 16;
+    uint64_t tj[2] = {0ull, 0ull}, sj[2] = {0ull, 0ull};
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+      if (64 * h >= nv) break;
+      const int k = 64 * h + lane;
+      bool tg = false, sm = false;
+      if (k < nv) ao_row_preds(visw[j * kFoVisw + k], a, r, c, combat, no_danger, tg, sm);
+      tj[h] = __ballot(tg);
+      sj[h] = __ballot(sm);
+    }
+    if (ja == j) t0 = tj[0], t1 = tj[1], s0 = sj[0], s1 = sj[1];
+  }
+  AoSections x;
+  x.s1[0] = t0;
+  x.s1[1] = t1 | noop;
+  x.s5[0] = item && !no_give ? s0 : 0ull;
+  x.s5[1] = (item && !no_give ? s1 : 0ull) | noop;
+  x.s7[0] = exch && !no_give ? s0 : 0ull;
+  x.s7[1] = (exch && !no_give ? s1 : 0ull) | noop;
+  const uint64_t ifr = (uint32_t)(bfr >> (16 * ja)) & 0xFFFFu;
+  x.s3 = (item ? ifr : 0ull) | 1ull << kInv;
+  x.s4 = (item && !no_give ? ifr : 0ull) | 1ull << kInv;
+  x.s9 = (exch ? (uint64_t)((uint32_t)(bse >> (16 * ja)) & 0xFFFFu) : 0ull) | 1ull << kInv;
+  x.s11 = (item ? (uint64_t)((uint32_t)(bus >> (16 * ja)) & 0xFFFFu) : 0ull) | 1ull << kInv;
+  x.s0 = combat ? low_bits(kSecN[0]) : 0ull;
+  x.s6[0] = x.s6[1] = x.s10[0] = x.s10[1] = 0ull;
+  if (exch) {
+    const int gold = own[la * kMirrorCols + F_GOLD];
+    const int ng = no_give ? min(gold, 1) : min(gold, kSecN[6]);
+    x.s6[0] = low_bits(ng);
+    x.s6[1] = low_bits(ng - 64);
+    x.s10[0] = low_bits(kSecN[10]);
+    x.s10[1] = low_bits(kSecN[10] - 64);
+    if constexpr (kWrap) {
+      const int pp = __shfl(my_prev, ja);
+      if ((p.wflags & kWrapObsPrice) && pp >= 0 && pp < kSecN[10]) {
+        const uint64_t clr = ~(1ull << (pp & 63));
+        if (pp < 64) x.s10[0] &= clr;
+        else x.s10[1] &= clr;
+      }
+    }
+  }
+  {  // 8 Move: ao_move_bits from the staged window rows
+    const uint8_t* wa = wsb + la * kFoWinAgentBytes;
+    uint32_t b = 0u;
+#pragma unroll
+    for (int d = 0; d < 5; d++)
+      if (!impassable((int)wa[(kVision + dir_dr(d)) * kFoWinRowBytes + kVision + dir_dc(d)])) b |= 1u << d;
+    x.s8 = b;
+  }
+  uint64_t m = 0ull;
+  fo_pass_chunks<0>(x, sl, m);
+  // Buy.MarketItem in the tracked chunks: word 0 (listings 0..63) in chunk 1, word 15 (listings from
+  // 960) in chunk 17 with the no-op bit; one ballot per agent over lane = listing
+  uint64_t bw0 = 0ull, bw15 = 0ull;
+  FoPass o;
+  o.lo = img.x;
+  o.hi = img.y;
+  if (exch && nm > 0) {
+    const uint32_t po0 = lane < nm ? mpo[lane] : 0u, po15 = 15 * 64 + lane < nm ? mpo[15 * 64 + lane] : 0u;
+#pragma unroll
+    for (int j = 0; j < kPerWave; j++) {
+      const int a = abase + kAoWaves * j;
+      const int gold = __builtin_amdgcn_readfirstlane((int)own[(w + kAoWaves * j) * kMirrorCols + F_GOLD]);
+      const uint64_t b0 = __ballot(lane < nm && (int)(po0 & 255u) <= gold && (int)(po0 >> 8) != a);
+      uint64_t b15 = 0ull;
+      if (nm > 15 * 64) b15 = __ballot(15 * 64 + lane < nm && (int)(po15 & 255u) <= gold && (int)(po15 >> 8) != a);
+      if (ja == j) bw0 = b0, bw15 = b15;
+      if (lane == kFoBuyLane + j) o.lo = (uint32_t)b0, o.hi = (uint32_t)(b0 >> 32);  // (else zero, as loaded)
+    }
+  }
+  if (sl == 1) m |= bw0 << (kWireBuyLo & 63);
+  if (sl == 2) m |= bw15 >> (64 - (kWireBuyLo & 63)) | 1ull << ((kWireBuyLo + NMMO_MARKET_ROWS) & 63);
+  // compare with what the rows hold; the new masks take the loaded ones' place
+  const bool ext = (zextv >> ja) & 1;
+  o.chg = __ballot(lane < 10 * kPerWave && (!ext || (uint32_t)m != img.x || (uint32_t)(m >> 32) != img.y));
+  if (lane < 10 * kPerWave) o.lo = (uint32_t)m, o.hi = (uint32_t)(m >> 32);
+  const int ji = min(lane / kInv, kPerWave - 1);
+  const uint2 iw = ist[(w + kAoWaves * ji) * kInv + lane % kInv];
+  const bool idl = lane < kInv * kPerWave && (!((zextv >> ji) & 1) || iw.x != pinv.x || iw.y != pinv.y);
+  o.idiff = __ballot(idl);
+  // the row state of the agents in the realm (a dead row's paths write their own): the masks and
+  // the position, the item words that changed, the tag and the state word
+  {
+    const int jp = lane < 10 * kPerWave ? ja : min(lane - 10 * kPerWave, kPerWave - 1);
+    const size_t ai = (size_t)e * P + min(abase + kAoWaves * jp, P - 1);
+    uint2 wv = make_uint2(o.lo, o.hi);
+    const int rcp = __shfl((int)my_rc, jp);  // (every lane, as ali below)
+    if (lane >= 10 * kPerWave) {
+      wv = make_uint2((uint32_t)((int)(int16_t)(rcp & 0xFFFF) | (rcp >> 16) << 8), 0u);
+    }
+    const int alp = __shfl(my_alive, jp);
+    if (lane < 11 * kPerWave && alp) reinterpret_cast<uint2*>(p.zext)[ai * kZext + (lane < 10 * kPerWave ? sl : 10)] = wv;
+    const size_t ii = (size_t)e * P + min(abase + kAoWaves * ji, P - 1);
+    const int ali = __shfl(my_alive, ji);  // (every lane: a cross-lane read under idl would miss lanes 0..3)
+    if (idl && ali) reinterpret_cast<uint2*>(p.zext)[ii * kZext + 11 + lane % kInv] = iw;
+    if (lane < kPerWave && my_alive) {
+      const size_t am = (size_t)e * P + abase + kAoWaves * lane;
+      if (!((zvalid >> lane) & 1)) p.zrow[am] = p.ztag;
+      p.zst[am] = zs_pack((my_nv + 1) & ~1, nm, my_task) | kZsExt;
+    }
+  }
+  return o;
 }
 
 // item_col (common.h) for a column fixed per lane (Inventory / Market chunks: lane L holds
@@ -479,7 +665,14 @@ __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per
   if (!img_ok) img = make_uint2(0u, 0u);
   if (!pinv_ok) pinv = make_uint2(0u, 0u);
   const int my_h = !zvl ? (kNObs | NMMO_MARKET_ROWS << 12) : zzl ? 0 : (zs_hv(my_s) | zs_hm(my_s) << 12);
-  int nrows = 0;                  // rows this wave wrote (rows_out[0])
+  // kMirror: every input of all of the wave's agents' masks is in LDS or registers here
+  FoPass mp{img.x, img.y, ~0ull, ~0ull};
+  if constexpr (kMirror) {
+    if (!(NMMO_FO_ABL & 1))
+      mp = fo_mask_pass<kWrap>(p, e, w, abase, nm, T, visw, wsb, ist, mpo, my_nv, my_rc, my_prev, my_alive, my_task, zvalid,
+                               zextv, img, pinv);
+  }
+  int nrows = 0;                 // rows this wave wrote (rows_out[0])
   unsigned long long nbytes = 0;  // bytes this wave stored (rows_out[1])
   int wo[2];
   ao_win_offsets<kFoWinRowBytes>(wo);
@@ -558,9 +751,16 @@ __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per
     uint32_t wm[4];
 #pragma unroll
     for (int i = 0; i < 4; i++) wm[i] = lane + 64 * i < 225 ? wa[ao_win_off(wo, i)] : 0u;
-    const uint2 it = lane < kInv ? ist[la * kInv + lane] : make_uint2(0u, 0u);
-    const uint32_t mv = ao_move_bits(wm[1]);
-    const int ninv = __builtin_ctzll(~__ballot(lane < kInv && it_type(it) != 0));  // occupied prefix
+    // (kMirror: the mask pass has read the item words and the Move tiles; the Inventory section
+    // reads the items when it is written)
+    uint2 it = make_uint2(0u, 0u);
+    uint32_t mv = 0u;
+    int ninv = 0;  // occupied prefix
+    if constexpr (!kMirror) {
+      it = lane < kInv ? ist[la * kInv + lane] : make_uint2(0u, 0u);
+      mv = ao_move_bits(wm[1]);
+      ninv = __builtin_ctzll(~__ballot(lane < kInv && it_type(it) != 0));
+    }
     int nv;
     if constexpr (kMirror) {  // compacted in the prologue
       nv = __builtin_amdgcn_readlane(my_nv, j);
@@ -575,7 +775,60 @@ __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per
     const bool ext = (zextv >> j) & 1;  // the row's extended state is valid
     FoImg fg{ext, img.x, img.y, 10 * j, 0, 0};
     // ActionTargets (+ AgentId, CurrentTick)
-    if (!(NMMO_FO_ABL & 1)) {
+    if constexpr (kMirror) {
+      // the tracked chunks the row does not hold, from the mask pass's lanes: two v_readlane, the
+      // lane's bit, one store each
+      if (!(NMMO_FO_ABL & 1)) {
+        const uint32_t chg = (uint32_t)(mp.chg >> (10 * j)) & 0x3FFu;
+        auto pm = [&](int l) {
+          return (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)mp.lo, l) |
+                 (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)mp.hi, l) << 32;
+        };
+        int nst = 0;
+        FO_STAMP(2);
+#pragma unroll 1
+        for (uint32_t cs = chg & 3u; cs; cs &= cs - 1u) {  // chunks 0 and 1
+          const int s = __builtin_ctz(cs);
+          fo_st(row, 64 * s + lane, fo_bit(pm(10 * j + s)));
+          nst += 64;
+        }
+        FO_STAMP(3);
+        auto buy_word = [&](int m) {  // as below
+          const int k = 64 * m + lane;
+          bool bv = false;
+          if (exch && k < nm) {
+            const uint32_t po = mpo[k];
+            bv = (int)(po & 255u) <= gold && (int)(po >> 8) != a;
+          }
+          return __ballot(bv);
+        };
+        const int clast = max(1, min((kWireBuyLo + max(nm, hm) - 1) >> 6, 16));
+        uint64_t bprev = pm(kFoBuyLane + j);
+#pragma unroll 1
+        for (int cc = 2; cc <= clast; cc++) {  // Buy-only chunks, not tracked
+          const uint64_t bcur = 64 * (cc - 1) < nm ? buy_word(cc - 1) : 0ull;
+          fo_st(row, 64 * cc + lane, fo_bit(bcur << (kWireBuyLo & 63) | bprev >> (64 - (kWireBuyLo & 63))));
+          bprev = bcur;
+        }
+        FO_STAMP(4);
+#pragma unroll 1
+        for (uint32_t cs = (chg >> 2) & 0x7Fu; cs; cs &= cs - 1u) {  // chunks 17 .. 23
+          const int s = __builtin_ctz(cs);
+          fo_st(row, 64 * (kFoTail0 + s) + lane, fo_bit(pm(10 * j + 2 + s)));
+          nst += 64;
+        }
+        constexpr int kc = kFoChunks - 1, n = kMaskN - 64 * kc;  // + AgentId, CurrentTick (fo_put)
+        if (chg >> 9) {
+          const uint64_t m = pm(10 * j + 9);
+          if (lane < n + 2) fo_st(row, 64 * kc + lane, lane < n ? fo_bit(m) : lane == n ? (float)aid : tickf);
+          nst += n + 2;
+        } else {
+          if (lane == n + 1) fo_st(row, 64 * kc + lane, tickf);
+          nst += 1;
+        }
+        nbytes += 4ull * (nst + 64 * (clast - 1));
+      }
+    } else if (!(NMMO_FO_ABL & 1)) {
       AoAgent ag;
       ag.a = a;
       ag.ti = tia;
@@ -673,10 +926,16 @@ __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per
     FO_STAMP(6);
     // Inventory: item q = 4 h + lane / 16, column lane % 16 (own items, owner = self); not stored
     // when the row was last written from the same 12 item words (its only inputs besides AgentId)
-    const int jl = (12 * j + lane) & 63;
-    const uint32_t px = (uint32_t)__shfl((int)pinv.x, jl), py = (uint32_t)__shfl((int)pinv.y, jl);
-    const bool inv_same = ext && __ballot(lane < kInv && (px != it.x || py != it.y)) == 0ull;
+    bool inv_same;
+    if constexpr (kMirror) {  // (compared by the mask pass)
+      inv_same = ((uint32_t)(mp.idiff >> (kInv * j)) & ((1u << kInv) - 1u)) == 0u;
+    } else {
+      const int jl = (12 * j + lane) & 63;
+      const uint32_t px = (uint32_t)__shfl((int)pinv.x, jl), py = (uint32_t)__shfl((int)pinv.y, jl);
+      inv_same = ext && __ballot(lane < kInv && (px != it.x || py != it.y)) == 0ull;
+    }
     if (!inv_same) {
+      if constexpr (kMirror) ninv = __builtin_ctzll(~__ballot(lane < kInv && it_type(ist[la * kInv + min(lane, kInv - 1)]) != 0));
 #pragma unroll
       for (int h = 0; h < ((NMMO_FO_ABL & 4) ? 0 : kInv * 16 / 64); h++) {
         const int q = 4 * h + iq;
@@ -726,7 +985,7 @@ __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per
     // as whole lines. (Round 5 skipped the row / column components when the agent had not moved: a
     // third of the stores, but every line of the section was still written in part, which HBM writes
     // as whole sectors -- WRITE_SIZE 1.9x the stored bytes; NMMO_FO_TILE_SKIP=1 keeps that variant.)
-    const uint32_t ppos = (uint32_t)__builtin_amdgcn_readlane((int)img.x, 40 + j);
+    const uint32_t ppos = (uint32_t)__builtin_amdgcn_readlane((int)(kMirror ? mp.lo : img.x), 40 + j);
     const bool tkn = NMMO_FO_TILE_SKIP && ext && !((ztile >> j) & 1);  // the Tile section holds what this kernel wrote
     const bool same_r = tkn && (int)(ppos & 255u) == r, same_c = tkn && (int)((ppos >> 8) & 255u) == c;
     if (!(NMMO_FO_ABL & 16)) {
@@ -749,7 +1008,8 @@ __global__ void __launch_bounds__(64 * kAoWaves) __attribute__((amdgpu_waves_per
       nbytes += 4ull * 225 * (1 + !same_r + !same_c);
     }
     FO_STAMP(10);
-    {  // the row's state: tag, zero thresholds and task, then the extended state
+    if constexpr (!kMirror) {  // the row's state: tag, zero thresholds and task, then the extended state
+                               // (kMirror: written by the mask pass for the wave's agents at once)
       uint32_t* zx = reinterpret_cast<uint32_t*>(kp->zext + ((size_t)e * P + a) * kZext);
       int wv = fg.nimg;  // lanes 0..19 the tracked masks, lanes 20 / 21 the position
       if (lane == 20) wv = r | c << 8;

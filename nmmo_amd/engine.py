@@ -302,6 +302,22 @@ class NmmoEngine:
                                                      self._stream()), "nmmo_obs_invalidate_sections")
         self._inv_ids = env_ids
 
+    def obs_row_state(self):
+        """Test hook of the hook build only (NMMO_LIB = build.HOOKS_PATH; nmmo_debug_obs_row_state is
+        not part of the nmmo_* ABI; flat obs layout): the obs row state after the device has drained, as
+        numpy arrays (valid [n, P] bool: the state describes the bound buffer; zst [n, P] and zext
+        [n, P, 23] uint64)."""
+        f = getattr(lib(), "nmmo_debug_obs_row_state", None)
+        if f is None:
+            raise NativeError("obs_row_state needs the hook build of the library (build.build_hooks, NMMO_LIB)")
+        f.argtypes, f.restype = [ctypes.c_void_p] * 5, ctypes.c_int
+        n, P = self.n_envs, self.P
+        tag = ctypes.c_uint64()
+        zrow, zst, zext = (np.zeros(s, np.uint64) for s in ((n, P), (n, P), (n, P, 23)))
+        with torch.cuda.device(self.device):
+            check(f(self.h, ctypes.byref(tag), zrow.ctypes.data, zst.ctypes.data, zext.ctypes.data), "nmmo_debug_obs_row_state")
+        return (zrow == np.uint64(tag.value)) & (tag.value != 0), zst, zext
+
     def get_fault(self) -> int:
         """The tick fault word (nmmo_get_fault: NMMO_FAULT_* | env << 8, 0 = none), then cleared."""
         f = ctypes.c_int32()
