@@ -193,6 +193,60 @@ NMH_API int nmh_item_logits_backward(const NmhItemHeads* ih, int32_t n_rows, con
                                      int64_t mask_stride, int32_t mask_kind, const float* g_out, int64_t g_stride,
                                      float* g_pq, void* stream);
 
+/* ---- Player encoder (SPEC.md §21): the reference's PlayerEncoder (baseline_policy.py:115-145) is
+ * two linear layers over a fixed 35-feature function x of an entity's 31 columns, so the mean pool
+ * of agent_fc needs only the sum of x over a row's entities, a pointer logit q . agent_fc(x_j) =
+ * (W^T q) . x_j + q . b needs only candidate j's own columns, and my_agent_fc needs x of one entity.
+ * No embedding tensor is made.
+ * x[0] = col 0; x[1 + i] = (i == t), i < 5, t = clamp(trunc(col 1), 0, 4), NaN gives 0;
+ * x[6 + k] = col (2 + k), k < 29. No column is scaled. */
+#define NMH_PLAYER_COLS 31
+#define NMH_PLAYER_FEATURES 35
+#define NMH_PLAYER_TYPES 5
+#define NMH_PLAYER_QUERY 40     /* floats per projected query: 35 weights, the constant, 4 pads */
+#define NMH_PLAYER_MAX_ROWS 256 /* entities per set */
+#define NMH_PLAYER_MAX_HEADS 4  /* heads over one set per call */
+
+#define NMH_PLAYER_F32 0 /* float32 elements (the flat obs row) */
+#define NMH_PLAYER_I16 1 /* int16 elements (the native obs), converted exactly */
+
+/* ents: set m's R x 31 entity columns read in place at ents + m * ent_stride elements of ent_kind's
+ * type (ent_stride >= 31 R; rows need no alignment beyond their element's; never written).
+ * ids: set m's AgentId read in place at ids + m * id_stride elements of id_kind's type (id_stride >= 1).
+ * features [n_sets, R, 35], sums [n_sets, 35], mine [n_sets, 35], mine_idx int32 [n_sets]: any may be
+ * NULL, not all four; ids may be NULL only if mine and mine_idx both are.
+ * sums[0], sums[6 + k] = the float32 sum of the raw column in one fixed order; sums[1 + i] = the number
+ * of entities of class i (exact). mine_idx[m] = the smallest j < R with col 0 == id and col 0 != 0,
+ * else 0 (a NaN id matches nothing); mine[m] = x of that entity.
+ * 1 <= R = set_rows <= NMH_PLAYER_MAX_ROWS; n_sets == 0 is a no-op. */
+NMH_API int nmh_player_features(int32_t n_sets, const void* ents, int64_t ent_stride, int32_t ent_kind,
+                                int32_t set_rows, const void* ids, int64_t id_stride, int32_t id_kind,
+                                float* features, float* sums, float* mine, int32_t* mine_idx, void* stream);
+
+typedef struct NmhPlayerHeads { /* 1..NMH_PLAYER_MAX_HEADS heads over one entity set */
+  int32_t n_heads;
+  int32_t mask_off[NMH_PLAYER_MAX_HEADS]; /* head h's first of set_rows + 1 entries in a mask row */
+  int32_t out_off[NMH_PLAYER_MAX_HEADS];  /* ... and in an out / g_out row */
+} NmhPlayerHeads;
+
+/* Obs row r reads entity set r. pq [n_rows, n_heads, 40], 16-byte aligned. out [n_rows, out_stride].
+ * Mask as in nmh_forward; both strides cover the furthest head's set_rows + 1 entries.
+ * out[r][out_off[h] + j], j < R legal: v = pq[35] + pq[1 + t]; v = fmaf(pq[0], col 0, v);
+ * v = fmaf(pq[6 + k], col (2 + k), v), k = 0..28. Illegal j and the no-op j = R: 0.0f. All R + 1
+ * entries are written, nothing else is, and an entity that no head of the call allows is never
+ * read. n_rows == 0 is a no-op. */
+NMH_API int nmh_player_logits(const NmhPlayerHeads* ph, int32_t n_rows, const void* ents, int64_t ent_stride,
+                              int32_t ent_kind, int32_t set_rows, const void* mask, int64_t mask_stride,
+                              int32_t mask_kind, const float* pq, float* out, int64_t out_stride, void* stream);
+
+/* g_pq [n_rows, n_heads, 40]: g_pq[f] = fmaf(g_out[j], (x_j, 1)[f], .) over the legal j < R in
+ * ascending order, f < 36; the four pads are written as 0. g_out [n_rows, g_stride] like out; its
+ * entries of illegal candidates and of the no-op are not read. No atomics: the same bits on every run. */
+NMH_API int nmh_player_logits_backward(const NmhPlayerHeads* ph, int32_t n_rows, const void* ents,
+                                       int64_t ent_stride, int32_t ent_kind, int32_t set_rows, const void* mask,
+                                       int64_t mask_stride, int32_t mask_kind, const float* g_out,
+                                       int64_t g_stride, float* g_pq, void* stream);
+
 NMH_API const char* nmh_last_error(void);
 /* "src=<hash of the sources the library was compiled from> arch=gfx950 fp_contract=off" */
 NMH_API const char* nmh_build_info(void);

@@ -1,0 +1,461 @@
+// player_enc.hip — the Entity path of the reference's observation encoder without its embeddings
+// (SPEC.md §21; include/nmmo_heads.h, nmh_player_features / nmh_player_logits /
+// nmh_player_logits_backward). Part of libnmmo_heads.so.
+//
+// PlayerEncoder.agent_fc is linear and its input x is a fixed 35-feature function of an entity's 31
+// columns (column 0, five npc_type one-hots, columns 2..30 raw), so
+//   mean_j agent_fc(x_j) = agent_fc(mean_j x_j)   -> the pool needs one 35-float sum per row,
+//   q . agent_fc(x_j)    = (W^T q) . x_j + q . b  -> a pointer logit needs the candidate's own 124 bytes,
+// and my_agent_fc needs the features of one entity row. No [N, R, H] embedding exists in forward and
+// no key gradient in backward.
+//
+// An entity row is 31 elements: never 16-byte aligned, and a lane per entity would make 31 loads 124
+// bytes apart. Every load of the Entity section here has consecutive lanes on consecutive elements.
+//
+// features / sums / own row: one 256-thread workgroup per set. Thread t < 248 is column t % 31 of slot
+// t / 31, so a pass reads 8 entities = 248 contiguous elements, four passes in flight. A thread keeps
+// the sum of its column over its entities in ascending order and one thread adds a column's 8
+// partial sums in ascending order; the class counts are LDS integer adds and the own row is an LDS
+// integer min over the matching j. With only the own row asked for, a wave per set reads column 0.
+//
+// logits: one wave per obs row, four rows per workgroup, no workgroup barrier. The wave reads the
+// heads' mask entries (lane j is candidate j, 64 at a time), stores 0 where a head forbids j, and
+// ballots the j that any head allows into an ascending LDS list with the allowing heads' bits. 64
+// listed candidates at a time, their 31 columns are copied into LDS (lane e takes element e % 31 of
+// listed candidate e / 31, four loads in flight) as float32 rows of 31 words: an odd stride, so the
+// lanes that then take one candidate each read without a bank conflict. A lane evaluates SPEC §21's
+// sum once per allowing head with the head's projected query in LDS. Entities no head allows are
+// never addressed.
+//
+// logits_backward: same grid, list and LDS rows, plus the listed candidates' g_out per head. Lane
+// f < 36 owns feature f and walks the list in ascending order: no atomics, the same bits on every run.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "common.h"
+#include "host_api.h"
+#include "../../include/nmmo_heads.h"
+
+using namespace nmmo;
+
+// heads.hip: the message goes into the error text nmh_last_error() returns
+int heads_record_error(int code, const char* msg);
+
+namespace {
+
+constexpr int kC = NMH_PLAYER_COLS, kF = NMH_PLAYER_FEATURES, kTypes = NMH_PLAYER_TYPES, kQ = NMH_PLAYER_QUERY;
+constexpr int kMaxRows = NMH_PLAYER_MAX_ROWS, kMaxHeads = NMH_PLAYER_MAX_HEADS;
+constexpr int kTypeCol = 1;
+constexpr int kRaw = kC - 2;  // features [6, 35) are columns [2, 31)
+constexpr int kThreads = 256, kSlots = kThreads / kC, kRowsPerBlock = 4, kChunk = 64;
+constexpr int kHeadShift = 12;  // a list entry is j | (the allowing heads' bits << 12)
+
+static_assert(kC == 31 && kF == 35 && kTypes == 5 && kQ == 40 && kRaw == 29 && kSlots == 8, "the start-kit entity row");
+static_assert(kMaxRows <= (1 << kHeadShift) && kMaxHeads <= 16 - kHeadShift, "a list entry is 16 bits");
+
+#define PLAYER_FAIL(code, ...) heads_record_error(fail(code, __VA_ARGS__), g_err.c_str())
+
+// SPEC §21's class rule: clamp(trunc(v), 0, 4), NaN -> 0
+__device__ inline int npc_class(float v) { return v >= 0.0f ? (v >= (float)(kTypes - 1) ? kTypes - 1 : (int)v) : 0; }
+
+// the column feature f < 35 depends on
+__device__ inline int feature_col(int f) { return f == 0 ? 0 : (f <= kTypes ? kTypeCol : f - kTypes + 1); }
+
+// column c's part of x [35]: feature 0, the five one-hots, or feature c + 4
+__device__ inline void put_x(float* __restrict__ x, int c, float v) {
+  if (c == kTypeCol) {
+    const int t = npc_class(v);
+#pragma unroll
+    for (int i = 0; i < kTypes; ++i) x[1 + i] = i == t ? 1.0f : 0.0f;
+  } else {
+    x[c == 0 ? 0 : c + kTypes - 1] = v;
+  }
+}
+
+__device__ inline float load_id(const void* __restrict__ ids, int64_t i, int id_kind) {
+  return id_kind == NMH_PLAYER_F32 ? static_cast<const float*>(ids)[i] : (float)static_cast<const int16_t*>(ids)[i];
+}
+
+__device__ __forceinline__ void wave_sync() {  // this wave's LDS stores before its later LDS loads
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+template <int MK>
+__device__ __forceinline__ bool legal_at(const void* mask, int64_t i) {
+  if (MK == NMH_MASK_F32) return static_cast<const float*>(mask)[i] > 0.f;
+  return static_cast<const uint8_t*>(mask)[i] != 0;
+}
+
+// ---------------------------------------------------------------- features, sums and the own row
+template <typename T>
+__global__ __launch_bounds__(kThreads) void nmh_player_features_kernel(
+    const T* __restrict__ ents, int64_t ent_stride, int R, const void* __restrict__ ids, int64_t id_stride,
+    int id_kind, float* __restrict__ features, float* __restrict__ sums, float* __restrict__ mine,
+    int32_t* __restrict__ mine_idx) {
+  constexpr int kU = 4;
+  __shared__ float s_part[kSlots][kC];
+  __shared__ int s_cnt[kTypes];
+  __shared__ int s_first;
+  const int tid = threadIdx.x, slot = tid / kC, c = tid % kC;
+  const int64_t m = blockIdx.x;
+  const bool own = mine || mine_idx;
+  if (tid < kTypes) s_cnt[tid] = 0;
+  if (tid == 0) s_first = R;
+  __syncthreads();
+  const T* __restrict__ set = ents + m * ent_stride;
+  float* __restrict__ fset = features ? features + m * (int64_t)R * kF : nullptr;
+  const float id = own ? load_id(ids, m * id_stride, id_kind) : 0.0f;
+  if (slot < kSlots) {
+    float acc = 0.0f;
+    for (int j0 = 0; j0 < R; j0 += kSlots * kU) {
+      T v[kU];
+#pragma unroll
+      for (int u = 0; u < kU; ++u) {
+        const int j = j0 + u * kSlots + slot;
+        v[u] = j < R ? set[(int64_t)j * kC + c] : (T)0;
+      }
+#pragma unroll
+      for (int u = 0; u < kU; ++u) {
+        const int j = j0 + u * kSlots + slot;
+        if (j < R) {
+          const float x = (float)v[u];
+          acc += x;
+          if (c == kTypeCol) atomicAdd(&s_cnt[npc_class(x)], 1);
+          if (c == 0 && own && x == id && x != 0.0f) atomicMin(&s_first, j);
+          if (fset) put_x(fset + (int64_t)j * kF, c, x);
+        }
+      }
+    }
+    s_part[slot][c] = acc;
+  }
+  __syncthreads();
+  if (sums && tid < kF) {
+    float s;
+    if (tid >= 1 && tid <= kTypes) {
+      s = (float)s_cnt[tid - 1];
+    } else {
+      const int col = feature_col(tid);
+      s = 0.0f;
+      for (int q = 0; q < kSlots; ++q) s += s_part[q][col];
+    }
+    sums[m * kF + tid] = s;
+  }
+  if (own) {
+    const int idx = s_first < R ? s_first : 0;
+    if (mine_idx && tid == 0) mine_idx[m] = idx;
+    if (mine && tid < kC) put_x(mine + m * kF, tid, (float)set[(int64_t)idx * kC + tid]);
+  }
+}
+
+// the own row alone: one wave per set reads column 0
+template <typename T>
+__global__ __launch_bounds__(64 * kRowsPerBlock) void nmh_player_own_kernel(
+    int n_sets, const T* __restrict__ ents, int64_t ent_stride, int R, const void* __restrict__ ids,
+    int64_t id_stride, int id_kind, float* __restrict__ mine, int32_t* __restrict__ mine_idx) {
+  const int w = __builtin_amdgcn_readfirstlane(wave_id()), lane = lane_id();
+  const int64_t m = (int64_t)blockIdx.x * kRowsPerBlock + w;
+  if (m >= n_sets) return;
+  const T* __restrict__ set = ents + m * ent_stride;
+  const float id = load_id(ids, m * id_stride, id_kind);
+  int idx = 0;
+  for (int b0 = 0; b0 < R; b0 += 64) {  // (wave-uniform: every lane ballots)
+    const int j = b0 + lane;
+    const float x = j < R ? (float)set[(int64_t)j * kC] : 0.0f;
+    const uint64_t b = __ballot(j < R && x == id && x != 0.0f);
+    if (b) {
+      idx = b0 + __builtin_ctzll(b);
+      break;
+    }
+  }
+  if (mine_idx && lane == 0) mine_idx[m] = idx;
+  if (mine && lane < kC) put_x(mine + m * kF, lane, (float)set[(int64_t)idx * kC + lane]);
+}
+
+// ---------------------------------------------------------------- pointer logits
+// The j < R that any head allows, ascending, into list[0, cnt) as j | heads << 12; returns cnt
+// (wave-uniform). ZERO: orow[out_off[h] + j] = 0 for every j < R head h forbids.
+template <int MK, bool ZERO>
+__device__ __forceinline__ int legal_list(const NmhPlayerHeads& ph, const void* __restrict__ mask, int64_t mbase, int R,
+                                          uint16_t* list, float* __restrict__ orow) {
+  const int H = ph.n_heads, lane = lane_id();
+  int cnt = 0;
+  for (int b0 = 0; b0 < R; b0 += 64) {  // (wave-uniform trip count: every lane ballots)
+    const int j = b0 + lane;
+    bool lg[kMaxHeads];
+#pragma unroll
+    for (int h = 0; h < kMaxHeads; ++h)  // unconditional loads, all in flight
+      lg[h] = h < H && legal_at<MK>(mask, mbase + ph.mask_off[h] + min(j, R - 1));
+    unsigned hm = 0;
+#pragma unroll
+    for (int h = 0; h < kMaxHeads; ++h) {
+      if (h < H && j < R) {
+        if (lg[h]) hm |= 1u << h;
+        else if (ZERO) orow[ph.out_off[h] + j] = 0.0f;
+      }
+    }
+    const uint64_t b = __ballot(hm != 0);
+    if (hm) list[cnt + __popcll(b & lanes_below())] = (uint16_t)(j | (hm << kHeadShift));
+    cnt += __popcll(b);
+  }
+  return cnt;
+}
+
+// The 31 columns of listed candidates [i0, i0 + n) into rows[n][31] as float32: lane e takes
+// element e % 31 of candidate e / 31, so a candidate's 31 elements are consecutive lanes' loads.
+template <typename T>
+__device__ __forceinline__ void stage_rows(const T* __restrict__ set, const uint16_t* list, int i0, int n,
+                                           float* rows) {
+  constexpr int kU = 4;
+  const int tot = n * kC;
+  for (int e0 = lane_id(); e0 < tot; e0 += 64 * kU) {
+    T v[kU];
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      const int e = e0 + 64 * u;
+      v[u] = (T)0;
+      if (e < tot) {
+        const int k = e / kC;
+        v[u] = set[(int64_t)(list[i0 + k] & ((1 << kHeadShift) - 1)) * kC + (e - k * kC)];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      const int e = e0 + 64 * u;
+      if (e < tot) rows[e] = (float)v[u];
+    }
+  }
+}
+
+// SPEC §21's sum of one candidate's LDS row with the head's projected query in LDS
+__device__ __forceinline__ float player_logit(const float* pq, const float* row) {
+  float v = pq[kF] + pq[1 + npc_class(row[kTypeCol])];
+  v = fmaf(pq[0], row[0], v);
+#pragma unroll
+  for (int k = 0; k < kRaw; ++k) v = fmaf(pq[1 + kTypes + k], row[2 + k], v);
+  return v;
+}
+
+template <typename T, int MK>
+__global__ __launch_bounds__(64 * kRowsPerBlock) void nmh_player_logits_kernel(
+    NmhPlayerHeads ph, int n_rows, const T* __restrict__ ents, int64_t ent_stride, int R,
+    const void* __restrict__ mask, int64_t ms, const float* __restrict__ pq, float* __restrict__ out, int64_t os) {
+  __shared__ float s_pq[kRowsPerBlock][kMaxHeads * kQ];
+  __shared__ float s_rows[kRowsPerBlock][kChunk * kC];
+  __shared__ uint16_t s_list[kRowsPerBlock][kMaxRows];
+  const int w = __builtin_amdgcn_readfirstlane(wave_id()), lane = lane_id();
+  const int64_t r = (int64_t)blockIdx.x * kRowsPerBlock + w;
+  if (r >= n_rows) return;  // (waves share nothing: no workgroup barrier below)
+  const int H = ph.n_heads;
+  float* spq = s_pq[w];
+  float* rows = s_rows[w];
+  uint16_t* list = s_list[w];
+  for (int i = lane; i < H * kQ; i += 64) spq[i] = pq[r * H * kQ + i];
+  const T* __restrict__ set = ents + r * ent_stride;
+  float* __restrict__ orow = out + r * os;
+  const int cnt = legal_list<MK, true>(ph, mask, r * ms, R, list, orow);
+#pragma unroll
+  for (int h = 0; h < kMaxHeads; ++h)
+    if (h < H && lane == h) orow[ph.out_off[h] + R] = 0.0f;  // the no-op entries
+  wave_sync();
+  for (int i0 = 0; i0 < cnt; i0 += kChunk) {
+    const int n = min(kChunk, cnt - i0);
+    stage_rows(set, list, i0, n, rows);
+    wave_sync();
+    if (lane < n) {
+      const int entry = list[i0 + lane], j = entry & ((1 << kHeadShift) - 1), hm = entry >> kHeadShift;
+      const float* row = rows + lane * kC;
+#pragma unroll
+      for (int h = 0; h < kMaxHeads; ++h)
+        if (h < H && (hm >> h & 1)) orow[ph.out_off[h] + j] = player_logit(spq + h * kQ, row);
+    }
+    wave_sync();  // the next chunk overwrites the rows
+  }
+}
+
+template <typename T, int MK>
+__global__ __launch_bounds__(64 * kRowsPerBlock) void nmh_player_logits_backward_kernel(
+    NmhPlayerHeads ph, int n_rows, const T* __restrict__ ents, int64_t ent_stride, int R,
+    const void* __restrict__ mask, int64_t ms, const float* __restrict__ g_out, int64_t gs, float* __restrict__ g_pq) {
+  __shared__ float s_rows[kRowsPerBlock][kChunk * kC];
+  __shared__ float s_g[kRowsPerBlock][kMaxHeads][kChunk];
+  __shared__ uint16_t s_list[kRowsPerBlock][kMaxRows];
+  const int w = __builtin_amdgcn_readfirstlane(wave_id()), f = lane_id();
+  const int64_t r = (int64_t)blockIdx.x * kRowsPerBlock + w;
+  if (r >= n_rows) return;  // (waves share nothing: no workgroup barrier below)
+  const int H = ph.n_heads;
+  float* rows = s_rows[w];
+  uint16_t* list = s_list[w];
+  const T* __restrict__ set = ents + r * ent_stride;
+  const float* __restrict__ grow = g_out + r * gs;
+  const int cnt = legal_list<MK, false>(ph, mask, r * ms, R, list, nullptr);
+  // the column feature f reads; the constant (f = 35) and the lanes beyond read column 0 and drop it
+  const int col = f < kF ? feature_col(f) : 0;
+  float acc[kMaxHeads] = {};
+  wave_sync();
+  for (int i0 = 0; i0 < cnt; i0 += kChunk) {
+    const int n = min(kChunk, cnt - i0);
+    stage_rows(set, list, i0, n, rows);
+    if (f < n) {  // lane k: listed candidate k's g_out in the heads that allow it, no other entry
+      const int entry = list[i0 + f], j = entry & ((1 << kHeadShift) - 1), hm = entry >> kHeadShift;
+#pragma unroll
+      for (int h = 0; h < kMaxHeads; ++h)
+        if (h < H && (hm >> h & 1)) s_g[w][h][f] = grow[ph.out_off[h] + j];
+    }
+    wave_sync();
+    if (f <= kF) {
+      for (int k = 0; k < n; ++k) {
+        const int hm = list[i0 + k] >> kHeadShift;  // (wave-uniform)
+        const float c = rows[k * kC + col];
+        float x = c;
+        if (f >= 1 && f <= kTypes) x = npc_class(c) == f - 1 ? 1.0f : 0.0f;
+        if (f == kF) x = 1.0f;
+#pragma unroll
+        for (int h = 0; h < kMaxHeads; ++h)
+          if (h < H && (hm >> h & 1)) acc[h] = fmaf(s_g[w][h][k], x, acc[h]);
+      }
+    }
+    wave_sync();  // the next chunk overwrites the rows and s_g
+  }
+  if (f < kQ) {
+#pragma unroll
+    for (int h = 0; h < kMaxHeads; ++h)
+      if (h < H) g_pq[(r * H + h) * kQ + f] = acc[h];  // the pads' lanes added nothing: 0
+  }
+}
+
+int launched(const char* fn) {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? NMH_OK : PLAYER_FAIL(NMH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
+}
+
+int check_set(const char* fn, const void* ents, int64_t ent_stride, int32_t ent_kind, int32_t set_rows) {
+  if (!ents) return PLAYER_FAIL(NMH_E_INVALID, "%s: ents is NULL", fn);
+  if (ent_kind != NMH_PLAYER_F32 && ent_kind != NMH_PLAYER_I16)
+    return PLAYER_FAIL(NMH_E_INVALID, "%s: unknown ent_kind %d", fn, ent_kind);
+  if (set_rows < 1 || set_rows > kMaxRows)
+    return PLAYER_FAIL(NMH_E_INVALID, "%s: set_rows %d outside 1..%d", fn, set_rows, kMaxRows);
+  if (ent_stride < (int64_t)kC * set_rows)
+    return PLAYER_FAIL(NMH_E_INVALID, "%s: ent_stride %lld < %d set_rows = %d", fn, (long long)ent_stride, kC,
+                       kC * set_rows);
+  return NMH_OK;
+}
+
+// the rules nmh_player_logits and its backward share; `out` names the [n_rows, out_stride] argument
+int check_logits(const char* fn, const NmhPlayerHeads* ph, int32_t n_rows, const void* ents, int64_t ent_stride,
+                 int32_t ent_kind, int32_t set_rows, const void* mask, int64_t mask_stride, int32_t mask_kind,
+                 const char* out_name, const void* out, const char* stride_name, int64_t out_stride) {
+  if (!ph) return PLAYER_FAIL(NMH_E_INVALID, "%s: ph is NULL", fn);
+  if (n_rows < 0) return PLAYER_FAIL(NMH_E_INVALID, "%s: n_rows %d is negative", fn, n_rows);
+  if (ph->n_heads < 1 || ph->n_heads > kMaxHeads)
+    return PLAYER_FAIL(NMH_E_INVALID, "%s: n_heads %d outside 1..%d", fn, ph->n_heads, kMaxHeads);
+  const int rc = check_set(fn, ents, ent_stride, ent_kind, set_rows);
+  if (rc != NMH_OK) return rc;
+  if (!mask) return PLAYER_FAIL(NMH_E_INVALID, "%s: mask is NULL", fn);
+  if (mask_kind != NMH_MASK_F32 && mask_kind != NMH_MASK_U8)
+    return PLAYER_FAIL(NMH_E_INVALID, "%s: unknown mask_kind %d", fn, mask_kind);
+  if (!out) return PLAYER_FAIL(NMH_E_INVALID, "%s: %s is NULL", fn, out_name);
+  for (int h = 0; h < ph->n_heads; ++h) {
+    if (ph->mask_off[h] < 0 || ph->out_off[h] < 0)
+      return PLAYER_FAIL(NMH_E_INVALID, "%s: mask_off[%d] %d or out_off[%d] %d is negative", fn, h, ph->mask_off[h],
+                         h, ph->out_off[h]);
+    if (mask_stride < (int64_t)ph->mask_off[h] + set_rows + 1)
+      return PLAYER_FAIL(NMH_E_INVALID, "%s: mask_stride %lld < mask_off[%d] + set_rows + 1 = %lld", fn,
+                         (long long)mask_stride, h, (long long)ph->mask_off[h] + set_rows + 1);
+    if (out_stride < (int64_t)ph->out_off[h] + set_rows + 1)
+      return PLAYER_FAIL(NMH_E_INVALID, "%s: %s %lld < out_off[%d] + set_rows + 1 = %lld", fn, stride_name,
+                         (long long)out_stride, h, (long long)ph->out_off[h] + set_rows + 1);
+  }
+  return NMH_OK;
+}
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+}  // namespace
+
+extern "C" {
+
+int nmh_player_features(int32_t n_sets, const void* ents, int64_t ent_stride, int32_t ent_kind, int32_t set_rows,
+                        const void* ids, int64_t id_stride, int32_t id_kind, float* features, float* sums,
+                        float* mine, int32_t* mine_idx, void* stream) {
+  const char* fn = "nmh_player_features";
+  if (n_sets < 0) return PLAYER_FAIL(NMH_E_INVALID, "%s: n_sets %d is negative", fn, n_sets);
+  const int rc = check_set(fn, ents, ent_stride, ent_kind, set_rows);
+  if (rc != NMH_OK) return rc;
+  if (!features && !sums && !mine && !mine_idx)
+    return PLAYER_FAIL(NMH_E_INVALID, "%s: features, sums, mine and mine_idx are all NULL", fn);
+  if (mine || mine_idx) {
+    if (!ids) return PLAYER_FAIL(NMH_E_INVALID, "%s: ids is NULL but mine or mine_idx is not", fn);
+    if (id_kind != NMH_PLAYER_F32 && id_kind != NMH_PLAYER_I16)
+      return PLAYER_FAIL(NMH_E_INVALID, "%s: unknown id_kind %d", fn, id_kind);
+    if (id_stride < 1) return PLAYER_FAIL(NMH_E_INVALID, "%s: id_stride %lld < 1", fn, (long long)id_stride);
+  }
+  if (n_sets == 0) return NMH_OK;
+  const bool f32 = ent_kind == NMH_PLAYER_F32;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (!features && !sums) {
+    const dim3 grid((unsigned)((n_sets + kRowsPerBlock - 1) / kRowsPerBlock)), block(64 * kRowsPerBlock);
+    if (f32)
+      hipLaunchKernelGGL(nmh_player_own_kernel<float>, grid, block, 0, st, n_sets, static_cast<const float*>(ents),
+                         ent_stride, set_rows, ids, id_stride, id_kind, mine, mine_idx);
+    else
+      hipLaunchKernelGGL(nmh_player_own_kernel<int16_t>, grid, block, 0, st, n_sets,
+                         static_cast<const int16_t*>(ents), ent_stride, set_rows, ids, id_stride, id_kind, mine,
+                         mine_idx);
+    return launched(fn);
+  }
+  const dim3 grid((unsigned)n_sets), block(kThreads);
+  if (f32)
+    hipLaunchKernelGGL(nmh_player_features_kernel<float>, grid, block, 0, st, static_cast<const float*>(ents),
+                       ent_stride, set_rows, ids, id_stride, id_kind, features, sums, mine, mine_idx);
+  else
+    hipLaunchKernelGGL(nmh_player_features_kernel<int16_t>, grid, block, 0, st, static_cast<const int16_t*>(ents),
+                       ent_stride, set_rows, ids, id_stride, id_kind, features, sums, mine, mine_idx);
+  return launched(fn);
+}
+
+#define PLAYER_LAUNCH(K, ...)                                                                             \
+  do {                                                                                                    \
+    const dim3 grid((unsigned)((n_rows + kRowsPerBlock - 1) / kRowsPerBlock)), block(64 * kRowsPerBlock); \
+    hipStream_t st = static_cast<hipStream_t>(stream);                                                    \
+    const bool mf = mask_kind == NMH_MASK_F32;                                                            \
+    if (ent_kind == NMH_PLAYER_F32) {                                                                     \
+      auto* kern = mf ? K<float, NMH_MASK_F32> : K<float, NMH_MASK_U8>;                                   \
+      hipLaunchKernelGGL(kern, grid, block, 0, st, *ph, n_rows, static_cast<const float*>(ents), __VA_ARGS__);   \
+    } else {                                                                                              \
+      auto* kern = mf ? K<int16_t, NMH_MASK_F32> : K<int16_t, NMH_MASK_U8>;                               \
+      hipLaunchKernelGGL(kern, grid, block, 0, st, *ph, n_rows, static_cast<const int16_t*>(ents), __VA_ARGS__); \
+    }                                                                                                     \
+  } while (0)
+
+int nmh_player_logits(const NmhPlayerHeads* ph, int32_t n_rows, const void* ents, int64_t ent_stride,
+                      int32_t ent_kind, int32_t set_rows, const void* mask, int64_t mask_stride, int32_t mask_kind,
+                      const float* pq, float* out, int64_t out_stride, void* stream) {
+  const char* fn = "nmh_player_logits";
+  const int rc = check_logits(fn, ph, n_rows, ents, ent_stride, ent_kind, set_rows, mask, mask_stride, mask_kind,
+                              "out", out, "out_stride", out_stride);
+  if (rc != NMH_OK) return rc;
+  if (!pq) return PLAYER_FAIL(NMH_E_INVALID, "%s: pq is NULL", fn);
+  if (!aligned16(pq)) return PLAYER_FAIL(NMH_E_INVALID, "%s: pq is not 16-byte aligned", fn);
+  if (n_rows == 0) return NMH_OK;
+  PLAYER_LAUNCH(nmh_player_logits_kernel, ent_stride, set_rows, mask, mask_stride, pq, out, out_stride);
+  return launched(fn);
+}
+
+int nmh_player_logits_backward(const NmhPlayerHeads* ph, int32_t n_rows, const void* ents, int64_t ent_stride,
+                               int32_t ent_kind, int32_t set_rows, const void* mask, int64_t mask_stride,
+                               int32_t mask_kind, const float* g_out, int64_t g_stride, float* g_pq, void* stream) {
+  const char* fn = "nmh_player_logits_backward";
+  const int rc = check_logits(fn, ph, n_rows, ents, ent_stride, ent_kind, set_rows, mask, mask_stride, mask_kind,
+                              "g_out", g_out, "g_stride", g_stride);
+  if (rc != NMH_OK) return rc;
+  if (!g_pq) return PLAYER_FAIL(NMH_E_INVALID, "%s: g_pq is NULL", fn);
+  if (n_rows == 0) return NMH_OK;
+  PLAYER_LAUNCH(nmh_player_logits_backward_kernel, ent_stride, set_rows, mask, mask_stride, g_out, g_stride, g_pq);
+  return launched(fn);
+}
+
+#undef PLAYER_LAUNCH
+
+}  // extern "C"

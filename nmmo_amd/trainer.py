@@ -21,6 +21,9 @@ by the obs ActionTargets (baseline_policy.py:245-262) — so the loop can be exe
 `ItemMaskedAgent` is the same stand-in with the reference's item path: the item encoder over
 Inventory and Market, their pooled embeddings and the five item pointer heads
 (baseline_policy.py:47-51, 148-190; SPEC.md §20).
+`PlayerMaskedAgent` is the same stand-in with the reference's player path: the player encoder over
+Entity, its pooled embedding, the row's own entity and the three entity pointer heads
+(baseline_policy.py:43-45, 115-145; SPEC.md §21).
 `RecurrentMaskedAgent` is the same stand-in with an LSTM between encoder and heads and the
 reference's recurrent convention, `agent(obs, state, action=None) -> (..., state)`: for an agent
 with an `.lstm` attribute the loop carries one LSTM state per agent slot through `evaluate()` and
@@ -307,6 +310,92 @@ class ItemMaskedAgent(MaskedLinearAgent):
                 padded = torch.cat([emb, emb.new_zeros(emb.shape[0], 1, emb.shape[2])], 1)
                 for k in ks:
                     parts[k] = torch.matmul(padded, queries[:, self.query_of[k]].unsqueeze(-1)).squeeze(-1)
+        return torch.cat(parts, 1)
+
+
+class PlayerMaskedAgent(MaskedLinearAgent):
+    """The stand-in with the reference's player path (baseline_policy.py:43-45, 52, 115-145, 222-230;
+    `nmmo_amd/player.py`, SPEC.md §21): a `PlayerEncoder` over the row's Entity [100, 31] section and
+    its AgentId. The hidden row is the parent's (materials and tick) plus a `Linear(hidden, hidden)`
+    over the pooled entity embedding plus a `Linear(hidden, hidden)` over `my_agent`, the embedding of
+    the row's own entity. The three `*.Target` heads are pointer heads over the entity embeddings,
+    each with a `Linear(hidden, hidden)` query scaled by 1 / sqrt(hidden) as in `PointerMaskedAgent`;
+    the other nine heads keep a `Linear(hidden, n)`. Either way the [N, 1586] logits go through the
+    parent's `masked`, so `fused_heads` works with both.
+
+    `fused_player=False` materialises the embeddings, pads the zero row and uses `matmul`, the
+    reference's way: 25 KB of entity embeddings per row at hidden 64. `fused_player=True` makes one
+    `player.player_own`, one `player.player_sums` and one `player.player_logits` call, reading the obs
+    rows in place, and holds no [N, 100, .] tensor. The call convention is the parent's."""
+
+    TARGETS = ("Attack.Target", "Give.Target", "GiveGold.Target")
+
+    def __init__(self, task_dim: int = 2048, hidden: int = 64, fused_heads: bool = False, seed: int = 0,
+                 fused_player: bool = False):
+        super().__init__(task_dim, hidden, fused_heads, seed)
+        from .player import PlayerEncoder
+
+        del self.actor  # every head has its own layer below
+        lay = layout.flat_layout(task_dim)
+        self.o_entity, self.o_id = lay["Entity"].offset, lay["AgentId"].offset
+        self.target_heads = [layout.HEAD[name] for name in self.TARGETS]
+        self.query_of = {k: p for p, k in enumerate(sorted(self.target_heads))}  # head -> its row of `queries`
+        self.player_encoder = PlayerEncoder(hidden, hidden, fused=fused_player)
+        self.players = nn.Linear(hidden, hidden)
+        self.my_agent = nn.Linear(hidden, hidden)
+        self.queries = nn.ModuleList(nn.Linear(hidden, hidden) for _ in self.target_heads)
+        self.dense = nn.ModuleList(nn.Linear(hidden, n) for k, n in enumerate(self.dims) if k not in self.query_of)
+        self.query_scale = 1.0 / math.sqrt(hidden)
+
+    def entities(self, obs: torch.Tensor):
+        """The rows' Entity sections and AgentId elements, as views of `obs`."""
+        return obs[:, self.o_entity:self.o_entity + layout.PLAYER_N_OBS * layout.ENTITY_COLS], obs[:, self.o_id]
+
+    def hidden(self, obs: torch.Tensor):
+        """(the hidden rows, the entity embeddings [N, 100, H] or None on the fused path)."""
+        mat = obs[:, self.o_tile + 2:self.o_tile + 3 * layout.TILE_ROWS:3] / 16.0
+        tick = obs[:, self.o_tick:self.o_tick + 1] / 1024.0
+        ents, ids = self.entities(obs)
+        enc = self.player_encoder
+        if enc.fused:
+            emb, pooled = None, enc.pooled(ents)
+        else:
+            emb = enc.embed(ents)
+            pooled = emb.mean(1)
+        h = self.encoder(torch.cat([mat, tick], 1)) + self.players(pooled) + self.my_agent(enc.my_agent(ents, ids))
+        return h, emb
+
+    def forward(self, obs: torch.Tensor, action: torch.Tensor | None = None):
+        h, emb = self.hidden(obs)
+        return self.masked(self.logits(h, obs, emb), h, obs, action)
+
+    def heads(self, h: torch.Tensor, obs: torch.Tensor, action: torch.Tensor | None = None):
+        enc = self.player_encoder
+        emb = None if enc.fused else enc.embed(self.entities(obs)[0])
+        return self.masked(self.logits(h, obs, emb), h, obs, action)
+
+    def logits(self, h, obs, emb=None):
+        """The twelve heads' logits [N, 1586] in head order. The unfused path takes the entity
+        embeddings; the fused path reads the rows (its illegal and no-op entries are 0)."""
+        queries = torch.stack([q(h) for q in self.queries], 1) * self.query_scale  # [N, 3, H]
+        parts = [None] * len(self.dims)
+        dense = iter(self.dense)
+        for k in range(len(self.dims)):
+            if k not in self.query_of:
+                parts[k] = next(dense)(h)
+        ks = sorted(self.target_heads)
+        if self.player_encoder.fused:
+            from .player import player_logits
+
+            width = layout.PLAYER_N_OBS + 1
+            pq = self.player_encoder.pointer_query(queries)
+            lg = player_logits(self.entities(obs)[0], pq, obs, [self.mask_off[k] for k in ks])
+            for k in ks:
+                parts[k] = lg[:, self.query_of[k] * width:(self.query_of[k] + 1) * width]
+        else:
+            padded = torch.cat([emb, emb.new_zeros(emb.shape[0], 1, emb.shape[2])], 1)
+            for k in ks:
+                parts[k] = torch.matmul(padded, queries[:, self.query_of[k]].unsqueeze(-1)).squeeze(-1)
         return torch.cat(parts, 1)
 
 
