@@ -29,7 +29,10 @@ R = 4  # lstm.ROWS, asserted below
 # (T, B, H, num_layers, state given)
 CASES = [(1, 1, 64, 1, True), (8, R - 1, 64, 2, False), (8, R + 1, 64, 1, True), (8, 130, 64, 2, True),
          (1, 130, 256, 1, False), (8, R + 1, 256, 1, True), (8, R - 1, 320, 2, True), (1, R + 1, 320, 1, False),
-         (8, 130, 320, 1, True), (2, R + 1, 1024, 1, True)]
+         (8, 130, 320, 1, True), (2, R + 1, 1024, 1, True),
+         # the slice edges of tests/test_gpu_lstm_shapes.py through the module: two slices at their largest H,
+         # one slice at its smallest, four slices at an H that is not a power of two
+         (8, 5, 512, 1, True), (8, 3, 576, 2, True), (8, 5, 192, 1, False)]
 PARAMS = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")
 
 
