@@ -143,6 +143,41 @@ NMH_API int nmh_tile_forward(int32_t n_rows, const void* tile, int64_t tile_stri
 NMH_API int nmh_tile_backward(int32_t n_rows, const uint8_t* idx, const float* out, const float* g_out,
                               int32_t n_chunks, float* g_table_parts, float* g_bias_parts, void* stream);
 
+/* ---- Tile encoder with the second convolution (SPEC.md §22): a1 = relu(conv1(embed(tile))) as
+ * above, kept on chip, then the reference's tile_conv_2 (32 -> 8 channels, 3 x 3) and its ReLU
+ * (baseline_policy.py:108). Only out2 [n_rows, 8, 11, 11], what tile_fc consumes, is written. */
+#define NMH_TILE2_CHANNELS 8     /* output channels of tile_conv_2 */
+#define NMH_TILE2_OUT 121        /* 11 x 11 output positions per channel */
+#define NMH_TILE2_FWD_ROWS 4     /* rows per workgroup of the forward kernel */
+#define NMH_TILE2_MAX_PARTS 1024 /* parts of rows whose g_w2 and g_bias2 are summed separately */
+
+/* tile, tile_stride, tile_kind, table, bias1 and idx_out as for nmh_tile_forward; a1 is its `out`,
+ * bit for bit, and is never stored. w2 [8, 32, 3, 3] and bias2 [8] are tile_conv_2's weight and bias,
+ * 16-byte aligned like table and bias1.
+ * out2[n][o2][y][x] = max(0, z), z = bias2[o2], then for c in 0..31, ky in 0..2, kx in 0..2 in that
+ * order z += w2[o2][c][ky][kx] * a1[n][c][y+ky][x+kx]: one float32 multiply and one float32 add per
+ * term, no contraction. out2 is contiguous and needs no alignment beyond a float's. */
+NMH_API int nmh_tile2_forward(int32_t n_rows, const void* tile, int64_t tile_stride, int32_t tile_kind,
+                              const float* table, const float* bias1, const float* w2, const float* bias2,
+                              float* out2, uint8_t* idx_out, void* stream);
+
+/* The gradients with respect to table, bias1, w2 and bias2, given idx and out2 as nmh_tile2_forward
+ * stored them, g_out2 like out2, and the forward's table, bias1 and w2 (16-byte aligned): a1 is
+ * recomputed from them. Two launches. The first takes part g of n_w2_parts (1..NMH_TILE2_MAX_PARTS),
+ * rows [g R, min(n_rows, (g+1) R)), R = ceil(n_rows / n_w2_parts), per workgroup: with
+ * dz2 = g_out2 where out2 > 0 and 0 elsewhere it writes
+ * dz1[n][c][y][x] = (a1 > 0) * sum over o2, ky, kx of w2[o2][c][ky][kx] * dz2[n][o2][y-ky][x-kx]
+ * to dz1_scratch [n_rows, 32, 13, 13] (16-byte aligned; transient, the caller neither fills nor
+ * reads it) and the part's sums to g_w2_parts [n_w2_parts, 8, 32, 3, 3] and g_bias2_parts
+ * [n_w2_parts, 8]. The second is nmh_tile_backward's kernel over dz1: n_table_chunks,
+ * g_table_parts [n_table_chunks, 3, 256, 9, 32] and g_bias1_parts [n_table_chunks, 32] as there.
+ * Every entry of every part is written (an empty part's are zeros) and the caller adds the parts.
+ * No atomics: the same bits on every run for a given (n_rows, n_table_chunks, n_w2_parts). */
+NMH_API int nmh_tile2_backward(int32_t n_rows, const uint8_t* idx, const float* out2, const float* g_out2,
+                               const float* table, const float* bias1, const float* w2, int32_t n_table_chunks,
+                               int32_t n_w2_parts, float* dz1_scratch, float* g_table_parts, float* g_bias1_parts,
+                               float* g_w2_parts, float* g_bias2_parts, void* stream);
+
 /* ---- Item encoder (SPEC.md §20): the reference's ItemEncoder (baseline_policy.py:148-170) is a
  * linear layer over a fixed 32-feature function x of an item's 16 columns, so its mean pool needs
  * only the sum of x over a set, and a pointer logit q . fc(x_j) = (W^T q) . x_j + q . b needs only

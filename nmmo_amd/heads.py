@@ -23,8 +23,8 @@ from . import _loader, build
 
 LIB_PATH = os.environ.get("NMMO_HEADS_LIB", build.lib_path("heads"))
 SYMBOLS = ["nmh_forward", "nmh_backward", "nmh_pointer_forward", "nmh_pointer_backward", "nmh_tile_forward",
-           "nmh_tile_backward", "nmh_item_features", "nmh_item_logits", "nmh_item_logits_backward", "nmh_player_features",
-           "nmh_player_logits", "nmh_player_logits_backward", "nmh_last_error", "nmh_build_info"]
+           "nmh_tile_backward", "nmh_tile2_forward", "nmh_tile2_backward", "nmh_item_features", "nmh_item_logits",
+           "nmh_item_logits_backward", "nmh_player_features", "nmh_player_logits", "nmh_player_logits_backward", "nmh_last_error", "nmh_build_info"]
 MAX_HEADS, MAX_DIM = 16, 2048
 MAX_SETS, MAX_KEY_DIM = 4, 256
 MASK_F32, MASK_U8 = 0, 1
@@ -56,6 +56,8 @@ def declare(L):
     L.nmh_backward.argtypes = [hp, i32, vp, i64, vp, i64, i32, vp, vp, vp, vp, vp, vp, i64, vp]
     L.nmh_tile_forward.argtypes = [i32, vp, i64, i32, vp, vp, vp, vp, vp]  # nmmo_amd/tile.py
     L.nmh_tile_backward.argtypes = [i32, vp, vp, vp, i32, vp, vp, vp]
+    L.nmh_tile2_forward.argtypes = [i32, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.nmh_tile2_backward.argtypes = [i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
     L.nmh_item_features.argtypes = [i32, vp, i64, i32, i32, vp, vp, vp]  # nmmo_amd/item.py
     L.nmh_item_logits.argtypes = [vp, i32, vp, i64, i32, i32, i32, vp, i64, i32, vp, vp, i64, vp]
     L.nmh_item_logits_backward.argtypes = [vp, i32, vp, i64, i32, i32, i32, vp, i64, i32, vp, i64, vp, vp]

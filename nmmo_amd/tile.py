@@ -15,7 +15,13 @@ tensor (86,400 B per row) is never made: backward keeps the 675 index bytes of a
     enc = TileEncoder(256, fused=True).cuda()
     h = enc(obs, offset=layout.flat_layout(task_dim)["Tile"].offset)      # flat obs rows, read in place
 
-There is no torch fallback for the fused path: a host tensor, or a missing library, is a `HeadsError`.
+`TileEncoder(fused=True, fused_conv2=True)` goes one layer further (`tile_conv12`, nmh_tile2_forward /
+nmh_tile2_backward, SPEC.md §22): `tile_conv_2` and its ReLU run in the same kernel on the LDS copy
+of the first convolution's result, so the [N, 32, 13, 13] activation (21,632 B per row) is never
+written and only the [N, 8, 11, 11] that `tile_fc` consumes leaves the kernel; backward recomputes
+the activation from the index bytes.
+
+There is no torch fallback for the fused paths: a host tensor, or a missing library, is a `HeadsError`.
 """
 
 from __future__ import annotations
@@ -35,6 +41,10 @@ FWD_ROWS = 4  # rows per workgroup of the forward kernel (NMH_TILE_FWD_ROWS)
 MAX_CHUNKS = 64
 CHUNK_ROWS = 16
 TILE_F32, TILE_I16 = 0, 1
+CHANNELS2, OUT2_SIDE = 8, 11  # tile_conv_2: 32 -> 8 channels, 13 x 13 -> 11 x 11 (NMH_TILE2_CHANNELS, NMH_TILE2_OUT)
+FWD2_ROWS = 4  # rows per workgroup of the fused forward kernel (NMH_TILE2_FWD_ROWS)
+MAX_W2_PARTS = 1024  # NMH_TILE2_MAX_PARTS
+W2_PART_ROWS = 4
 
 
 def n_chunks_for(n_rows: int) -> int:
@@ -44,6 +54,18 @@ def n_chunks_for(n_rows: int) -> int:
     chunk put a workgroup on every one of 256 compute units from 152 rows on; at the cap the
     partial tables the caller adds are 64 x 884,736 B = 57 MB."""
     return max(1, min(MAX_CHUNKS, -(-int(n_rows) // CHUNK_ROWS)))
+
+
+def n_w2_parts_for(n_rows: int) -> int:
+    """The number of row parts `tile_conv12`'s backward sums `g_w2` and `g_bias2` over separately:
+    ceil(N / 4), at most NMH_TILE2_MAX_PARTS = 1,024. A function of N alone, so a given batch size
+    always adds in the same order. One workgroup of 256 threads works on a part, three to a compute
+    unit by registers, so 1,024 parts are one full round over 256 compute units with one to spare
+    and are reached at 4,096 rows, and a minibatch of 1,024 rows already gives every compute unit
+    a workgroup. Four rows per part keep the part's own store (9,248 B) below a tenth of the
+    4 x 21,632 B of `dz1` the same workgroup writes; at the cap the parts the caller adds are
+    1,024 x 9,248 B = 9.5 MB, a sixth of the table's 57 MB."""
+    return max(1, min(MAX_W2_PARTS, -(-int(n_rows) // W2_PART_ROWS)))
 
 
 def tile_table(embedding_weight: torch.Tensor, conv1_weight: torch.Tensor) -> torch.Tensor:
@@ -145,6 +167,68 @@ def tile_conv1(obs_or_tile: torch.Tensor, table: torch.Tensor, bias: torch.Tenso
     return _TileConv1.apply(obs_or_tile, table, bias, kind)
 
 
+class _TileConv12(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, table, bias1, weight2, bias2, kind):
+        if not (x.is_cuda and table.is_cuda and bias1.is_cuda and weight2.is_cuda and bias2.is_cuda):
+            raise HeadsError("tile_conv12 runs on the GPU: tile, table, weights and biases must be device tensors")
+        if tuple(table.shape) != (FEATURES, VALUES, TAPS, CHANNELS) or tuple(bias1.shape) != (CHANNELS,):
+            raise ValueError(f"table must be [3, 256, 9, 32] and bias1 [32], got {tuple(table.shape)}, {tuple(bias1.shape)}")
+        if tuple(weight2.shape) != (CHANNELS2, CHANNELS, 3, 3) or tuple(bias2.shape) != (CHANNELS2,):
+            raise ValueError(f"weight2 must be [8, 32, 3, 3] and bias2 [8], got {tuple(weight2.shape)}, {tuple(bias2.shape)}")
+        x, stride, kind = _tile_arg(x.detach(), kind)
+        n, dev = x.shape[0], x.device
+        tab, b1, w2, b2 = _dense16(table), _dense16(bias1), _dense16(weight2), _dense16(bias2)
+        keep = any(ctx.needs_input_grad)  # all False under no_grad
+        out2 = torch.empty((n, CHANNELS2, OUT2_SIDE, OUT2_SIDE), dtype=torch.float32, device=dev)
+        idx = torch.empty((n, TILES, FEATURES), dtype=torch.uint8, device=dev) if keep else None
+        with torch.cuda.device(dev):
+            heads.check(heads.lib().nmh_tile2_forward(
+                n, x.data_ptr(), stride, kind, tab.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
+                out2.data_ptr(), None if idx is None else idx.data_ptr(), heads._stream()), "nmh_tile2_forward")
+        if keep:
+            ctx.save_for_backward(idx, out2, table, bias1, weight2)  # the last three are the caller's own tensors
+        return out2
+
+    @staticmethod
+    def backward(ctx, g_out2):
+        idx, out2, table, bias1, weight2 = ctx.saved_tensors
+        tab, b1, w2 = _dense16(table), _dense16(bias1), _dense16(weight2)
+        n, dev = out2.shape[0], out2.device
+        chunks, parts = n_chunks_for(n), n_w2_parts_for(n)
+        g_out2 = g_out2.detach().to(torch.float32).contiguous()
+
+        def empty(*shape):
+            return torch.empty(shape, dtype=torch.float32, device=dev)
+
+        dz1 = empty(n, CHANNELS, OUT_SIDE, OUT_SIDE)  # transient: freed when backward returns
+        g_table, g_bias1 = empty(chunks, FEATURES, VALUES, TAPS, CHANNELS), empty(chunks, CHANNELS)
+        g_w2, g_bias2 = empty(parts, CHANNELS2, CHANNELS, 3, 3), empty(parts, CHANNELS2)
+        with torch.cuda.device(dev):
+            heads.check(heads.lib().nmh_tile2_backward(
+                n, idx.data_ptr(), out2.data_ptr(), g_out2.data_ptr(), tab.data_ptr(), b1.data_ptr(), w2.data_ptr(),
+                chunks, parts, dz1.data_ptr(), g_table.data_ptr(), g_bias1.data_ptr(), g_w2.data_ptr(),
+                g_bias2.data_ptr(), heads._stream()), "nmh_tile2_backward")
+        if n == 0:
+            for t in (g_table, g_bias1, g_w2, g_bias2):
+                t.zero_()
+        return None, g_table.sum(0), g_bias1.sum(0), g_w2.sum(0), g_bias2.sum(0), None
+
+
+def tile_conv12(obs_or_tile: torch.Tensor, table: torch.Tensor, bias1: torch.Tensor, weight2: torch.Tensor,
+                bias2: torch.Tensor, *, kind=None) -> torch.Tensor:
+    """relu(tile_conv_2(relu(tile_conv_1(embedding(tile))))) [N, 8, 11, 11] as one kernel (SPEC.md §22).
+
+    obs_or_tile, table, bias1 and kind as for `tile_conv1`; weight2 [8, 32, 3, 3] and bias2 [8] are
+    `tile_conv_2`'s. The first convolution's [N, 32, 13, 13] result lives in LDS only. With grad
+    enabled the call keeps the rows' indices (uint8 [N, 225, 3]), its output and references to
+    `table`, `bias1` and `weight2`: backward recomputes the first activation from them, so the obs
+    buffer may be rewritten in between. Backward allocates a transient [N, 32, 13, 13] buffer and sums
+    the gradients over `n_chunks_for(N)` chunks (table, bias1) and `n_w2_parts_for(N)` parts
+    (weight2, bias2) of rows without atomics: the same bits on every run."""
+    return _TileConv12.apply(obs_or_tile, table, bias1, weight2, bias2, kind)
+
+
 class TileEncoder(nn.Module):
     """The reference's TileEncoder (baseline_policy.py:85-112), parameter names and shapes included,
     so a `state_dict` moves both ways. `forward(obs, offset)` takes rows whose columns
@@ -154,11 +238,15 @@ class TileEncoder(nn.Module):
 
     `fused=False` is the reference's chain in torch. `fused=True` replaces embedding, `tile_conv_1`
     and the first ReLU by `tile_conv1`, reading the rows in place; `tile_conv_2` and `tile_fc` stay
-    with torch."""
+    with torch. `fused_conv2=True` (needs `fused=True`) makes `forward` run `tile_conv_2` and its
+    ReLU in the same kernel too (`tile_conv12`); `tile_fc` stays with torch."""
 
-    def __init__(self, input_size: int, fused: bool = False):
+    def __init__(self, input_size: int, fused: bool = False, fused_conv2: bool = False):
         super().__init__()
+        if fused_conv2 and not fused:
+            raise ValueError("fused_conv2=True extends the fused path: it needs fused=True")
         self.fused = bool(fused)
+        self.fused_conv2 = bool(fused_conv2)
         self.register_buffer("tile_offset", torch.tensor([i * VALUES for i in range(FEATURES)]), persistent=False)
         self.embedding = nn.Embedding(FEATURES * VALUES, EMBED)
         self.tile_conv_1 = nn.Conv2d(FEATURES * EMBED, CHANNELS, 3)
@@ -180,6 +268,13 @@ class TileEncoder(nn.Module):
         return F.relu(self.tile_conv_1(tile))
 
     def forward(self, obs: torch.Tensor, offset: int = 0) -> torch.Tensor:
+        if self.fused_conv2:
+            if obs.dim() == 3:
+                obs = obs.reshape(obs.shape[0], -1)
+            table = tile_table(self.embedding.weight, self.tile_conv_1.weight)
+            tile = tile_conv12(obs[:, offset:offset + ROW], table, self.tile_conv_1.bias, self.tile_conv_2.weight,
+                               self.tile_conv_2.bias)
+            return F.relu(self.tile_fc(tile.view(tile.shape[0], -1)))
         tile = F.relu(self.tile_conv_2(self.conv1(obs, offset)))
         tile = tile.contiguous().view(tile.shape[0], -1)
         return F.relu(self.tile_fc(tile))

@@ -206,14 +206,15 @@ class TileMaskedAgent(MaskedLinearAgent):
     linear layer; `nmmo_amd/tile.py`) over the row's Tile section, then the tick and one hidden
     layer as in the parent. `fused_tile=True` runs the embedding, the first convolution and its
     ReLU as one `tile.tile_conv1` call (the HIP kernels of SPEC.md §19), reading the obs rows in
-    place. The call convention is the parent's."""
+    place; `fused_tile_conv2=True` (with `fused_tile`) runs the second convolution and its ReLU in
+    that kernel too (`tile.tile_conv12`, SPEC.md §22). The call convention is the parent's."""
 
     def __init__(self, task_dim: int = 2048, hidden: int = 64, fused_heads: bool = False, seed: int = 0,
-                 fused_tile: bool = False):
+                 fused_tile: bool = False, fused_tile_conv2: bool = False):
         super().__init__(task_dim, hidden, fused_heads, seed)
         from .tile import TileEncoder
 
-        self.tile_encoder = TileEncoder(hidden, fused=fused_tile)
+        self.tile_encoder = TileEncoder(hidden, fused=fused_tile, fused_conv2=fused_tile_conv2)
         self.encoder = nn.Sequential(nn.Linear(hidden + 1, hidden), nn.ReLU())
 
     def forward(self, obs: torch.Tensor, action: torch.Tensor | None = None):

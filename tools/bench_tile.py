@@ -11,6 +11,11 @@ rows time only the part the kernel replaces (embedding + tile_conv_1 + ReLU), "e
 whole module. Bytes per row are the algorithmic ones: the unfused chain writes and keeps the
 [96, 15, 15] float32 embedding tensor (86,400 B), the fused one the 675 index bytes.
 
+The "encoder" rows carry a third variant, `fused=True, fused_conv2=True` (SPEC.md §22: the second
+convolution in the same kernel, the [32, 13, 13] activation of 21,632 B per row never written), in
+the same windows and alternation, as `fused_conv2_*` keys; `encoder_max_abs_difference` holds the
+three paths' pairwise largest output differences.
+
 Usage (GPU box): python tools/bench_tile.py [rows ...] [--iters N] [--repeats N] [--out FILE]
 """
 
@@ -25,7 +30,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 from nmmo_amd import layout  # noqa: E402
-from nmmo_amd.tile import ROW, TileEncoder, n_chunks_for  # noqa: E402
+from nmmo_amd.tile import ROW, TileEncoder, n_chunks_for, n_w2_parts_for  # noqa: E402
 
 OBS_ELEMS = 23987
 
@@ -68,13 +73,15 @@ def bench_rows(rows, iters, repeats):
     g = torch.Generator(device="cuda").manual_seed(1)
     obs, off = make_obs(rows, g)
     torch.manual_seed(2)
-    enc = {True: TileEncoder(256, fused=True).cuda(), False: TileEncoder(256, fused=False).cuda()}
+    enc = {True: TileEncoder(256, fused=True).cuda(), False: TileEncoder(256, fused=False).cuda(),
+           "conv2": TileEncoder(256, fused=True, fused_conv2=True).cuda()}
     enc[False].load_state_dict(enc[True].state_dict())
+    enc["conv2"].load_state_dict(enc[True].state_dict())
     w_out = torch.randn((rows, 256), device="cuda", generator=g)
     w_c1 = torch.randn((rows, 32, 13, 13), device="cuda", generator=g)
 
-    def call(fused, part, grad):
-        m = enc[fused]
+    def call(variant, part, grad):
+        m = enc[variant]
 
         def fn():
             if not grad:
@@ -87,29 +94,44 @@ def bench_rows(rows, iters, repeats):
         return fn
 
     out = {"rows": rows, "iters": iters, "repeats": repeats, "backward_chunks": n_chunks_for(rows),
-           "embedding_bytes_per_row_unfused": 96 * 225 * 4, "index_bytes_per_row_fused": ROW}
+           "backward_w2_parts": n_w2_parts_for(rows),
+           "embedding_bytes_per_row_unfused": 96 * 225 * 4, "index_bytes_per_row_fused": ROW,
+           "conv1_bytes_per_row_not_written_by_fused_conv2": 32 * 13 * 13 * 4}
     with torch.no_grad():
         a, b = enc[True].conv1(obs, off), enc[False].conv1(obs, off)
         out["conv1_max_abs_difference"] = float((a - b).abs().max())
+        del a, b
+        h = {name: enc[v](obs, off) for v, name in ((True, "fused"), (False, "unfused"), ("conv2", "fused_conv2"))}
+        out["encoder_max_abs_difference"] = {f"{p}_vs_{q}": float((h[p] - h[q]).abs().max()) for p, q in
+                                             (("fused_conv2", "fused"), ("fused_conv2", "unfused"), ("fused", "unfused"))}
+        del h
     for part in ("conv1", "encoder"):
+        # conv1() of the third variant is the second's: it enters the encoder rows only
+        variants = [(True, "fused"), (False, "unfused")] + ([("conv2", "fused_conv2")] if part == "encoder" else [])
         for grad in (False, True):
-            fns = {fused: call(fused, part, grad) for fused in (True, False)}
+            fns = {v: call(v, part, grad) for v, _ in variants}
             for fn in fns.values():  # warm up: code objects, MIOpen's algorithm search, the allocator
                 for _ in range(3):
                     fn()
             torch.cuda.synchronize()
-            times = {True: [], False: []}
+            times = {v: [] for v, _ in variants}
             for _ in range(repeats):
-                for fused in (True, False):
-                    times[fused].append(window(fns[fused], iters))
+                for v, _ in variants:
+                    times[v].append(window(fns[v], iters))
             key = f"{part}_{'forward_backward' if grad else 'forward_no_grad'}"
             r = {}
-            for fused, name in ((True, "fused"), (False, "unfused")):
-                r[name + "_us"] = {"median": round(statistics.median(times[fused]), 1),
-                                   "min": round(min(times[fused]), 1), "max": round(max(times[fused]), 1)}
-                r[name + "_peak_bytes"] = peak(fns[fused])
+            for v, name in variants:
+                r[name + "_us"] = {"median": round(statistics.median(times[v]), 1),
+                                   "min": round(min(times[v]), 1), "max": round(max(times[v]), 1)}
+                r[name + "_peak_bytes"] = peak(fns[v])
             r["unfused_over_fused_time"] = round(r["unfused_us"]["median"] / r["fused_us"]["median"], 2)
             r["unfused_over_fused_peak"] = round(r["unfused_peak_bytes"] / max(1, r["fused_peak_bytes"]), 2)
+            if part == "encoder":
+                r["fused_over_fused_conv2_time"] = round(r["fused_us"]["median"] / r["fused_conv2_us"]["median"], 2)
+                r["fused_minus_fused_conv2_peak_bytes"] = r["fused_peak_bytes"] - r["fused_conv2_peak_bytes"]
+                lo, hi = r["fused_conv2_us"], r["fused_us"]
+                r["fused_conv2_vs_fused"] = ("faster" if lo["max"] < hi["min"] else
+                                             "slower" if lo["min"] > hi["max"] else "tie")  # ranges must not overlap
             out[key] = r
     return out
 
