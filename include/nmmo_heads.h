@@ -282,6 +282,62 @@ NMH_API int nmh_player_logits_backward(const NmhPlayerHeads* ph, int32_t n_rows,
                                        int64_t mask_stride, int32_t mask_kind, const float* g_out,
                                        int64_t g_stride, float* g_pq, void* stream);
 
+/* ---- Decoder (SPEC.md §23): every action head of a row from the obs row itself, in one launch.
+ * A head is dense (its logits are given) or a pointer head into one of up to NMH_MAX_SETS candidate
+ * sets that are read in place; a pointer head's logits are §20's (item sets) or §21's (entity sets)
+ * and go straight into the masked categorical of §15. The call equals, bit for bit,
+ * nmh_forward / nmh_backward on the logits row that nmh_item_logits / nmh_player_logits and the dense
+ * logits would make, with the *_logits_backward calls behind it; that row is never made. */
+#define NMH_SET_ENTITY 0 /* SPEC §21: 31 columns, 35 features, 1..NMH_PLAYER_MAX_ROWS candidates */
+#define NMH_SET_ITEM 1   /* SPEC §20: 16 columns, 32 features, 1..NMH_ITEM_MAX_ROWS candidates */
+#define NMH_ELEM_F32 0   /* float32 candidate columns (the flat obs row) */
+#define NMH_ELEM_I16 1   /* int16 candidate columns (the native obs), converted exactly */
+#define NMH_DECODER_QUERY 40 /* floats per pointer head in pq and g_pq */
+
+/* Set s has set_rows[s] = R candidates of rule[s]'s columns, read in place for obs row r at
+ * base[s] + (r / share[s]) * stride[s] elements of elem_kind's type: stride[s] >= columns * R,
+ * share[s] >= 1 (1 for flat rows, the players per env for the native per-env Market). One elem_kind
+ * holds for all sets of a call; rows need no alignment beyond their element's and are never written.
+ * head_set[k] = -1: head k is dense; else head k points into set head_set[k] and dims[k] == R + 1,
+ * the last entry being the no-op whose logit is exactly 0.0f. 0 <= n_sets <= NMH_MAX_SETS, every
+ * set is used by a head, and sum(dims) <= NMH_MAX_DIM. base holds DEVICE pointers. */
+typedef struct NmhDecoderSets {
+  int32_t n_sets;
+  int32_t elem_kind;
+  int32_t rule[NMH_MAX_SETS];
+  int32_t set_rows[NMH_MAX_SETS];
+  int32_t share[NMH_MAX_SETS];
+  int32_t head_set[NMH_MAX_HEADS];
+  int64_t stride[NMH_MAX_SETS];
+  const void* base[NMH_MAX_SETS];
+} NmhDecoderSets;
+
+/* pq [n_rows, P, 40], 16-byte aligned: one slot per pointer head in head order (NULL iff P == 0). An
+ * item head reads floats 0..32 of its slot as nmh_item_logits reads a projected query, an entity
+ * head 0..35 as nmh_player_logits does; the rest of a slot is ignored. dense [n_rows, dense_stride]:
+ * the dense heads' logits in head order (NULL iff no head is dense). mask, mask_stride, mask_kind,
+ * actions_in, seed, offset, row_base and the five outputs are nmh_forward's. A candidate that its
+ * head's mask forbids is never addressed. Dynamic LDS stays below 64 KiB: four rows per workgroup
+ * where four waves fit (the nmmo heads: 63,040 bytes), else two. n_rows == 0 is a no-op. */
+NMH_API int nmh_decoder_forward(const NmhHeads* hd, const NmhDecoderSets* sets, int32_t n_rows, const float* pq,
+                                const float* dense, int64_t dense_stride, const void* mask, int64_t mask_stride,
+                                int32_t mask_kind, const int32_t* actions_in, uint64_t seed, uint64_t offset,
+                                uint32_t row_base, int32_t* actions_out, float* logprob, float* entropy,
+                                float* lse, float* head_entropy, void* stream);
+
+/* The gradient of sum_r g_logprob[r] logprob[r] + g_entropy[r] entropy[r] (either may be NULL = zeros):
+ * g_dense [n_rows, g_dense_stride] like nmh_backward's g_logits over the dense heads, every entry
+ * written, zeros included; g_pq like pq (16-byte aligned): g_pq[f] = fmaf(g_j, (x_j, 1)[f], .) over the
+ * head's legal j < R in ascending order, g_j being nmh_backward's expression on the recomputed logit,
+ * and the floats of a slot that forward ignores written as 0. g_dense or g_pq may be NULL: it is not
+ * computed, and a head none of whose gradients is wanted is skipped. No atomics: the same bits on
+ * every run. */
+NMH_API int nmh_decoder_backward(const NmhHeads* hd, const NmhDecoderSets* sets, int32_t n_rows, const float* pq,
+                                 const float* dense, int64_t dense_stride, const void* mask, int64_t mask_stride,
+                                 int32_t mask_kind, const int32_t* actions, const float* lse,
+                                 const float* head_entropy, const float* g_logprob, const float* g_entropy,
+                                 float* g_dense, int64_t g_dense_stride, float* g_pq, void* stream);
+
 NMH_API const char* nmh_last_error(void);
 /* "src=<hash of the sources the library was compiled from> arch=gfx950 fp_contract=off" */
 NMH_API const char* nmh_build_info(void);

@@ -29,33 +29,23 @@
 
 #include "common.h"
 #include "host_api.h"
+#include "item_dev.h"  // load_item, item_logit, item_feature, item_class: shared with decoder.hip
 #include "../../include/nmmo_heads.h"
 
 using namespace nmmo;
+using namespace nmmo::item_dev;
 
 // heads.hip: the message goes into the error text nmh_last_error() returns
 int heads_record_error(int code, const char* msg);
 
 namespace {
 
-constexpr int kC = NMH_ITEM_COLS, kF = NMH_ITEM_FEATURES, kTypes = NMH_ITEM_TYPES, kQ = NMH_ITEM_QUERY;
 constexpr int kMaxRows = NMH_ITEM_MAX_ROWS, kMaxHeads = NMH_ITEM_MAX_HEADS;
-constexpr int kDiscrete = kTypes + 2;  // features [0, 20) are one-hots, [20, 32) scaled columns
-constexpr int kCont = kF - kDiscrete;  // 12
-constexpr int kTypeCol = 1, kEquipCol = 14;
 constexpr int kThreads = 256, kRowsPerBlock = 4;
-constexpr float kScale = 0.01f;
 
 static_assert(kC == 16 && kF == 32 && kTypes == 18 && kQ == 36 && kCont == 12, "the start-kit item row");
 
 #define ITEM_FAIL(code, ...) heads_record_error(fail(code, __VA_ARGS__), g_err.c_str())
-
-// the item column behind scaled feature 20 + k: 3, 4, ..., 13, 15
-__host__ __device__ constexpr int cont_col(int k) { return k < kCont - 1 ? 3 + k : 15; }
-
-// SPEC §20's class rule: clamp(trunc(v), 0, hi), NaN -> 0
-__device__ inline int item_class(float v, int hi) { return v >= 0.0f ? (v >= (float)hi ? hi : (int)v) : 0; }
-__device__ inline int item_class(int16_t v, int hi) { return v < 0 ? 0 : (v > hi ? hi : (int)v); }
 
 // lane `src`'s value of v (every lane of the wave takes part)
 __device__ inline float shfl_item(float v, int src) { return __shfl(v, src); }
@@ -143,43 +133,6 @@ __global__ __launch_bounds__(kThreads) void nmh_item_features_kernel(
 }
 
 // ---------------------------------------------------------------- pointer logits
-struct Item {
-  int type, equipped;
-  float x[kCont];  // features 20..31
-};
-
-// The 16 columns of one item, wherever it lies: four (two) 16-byte loads when the item is 16-byte
-// aligned, else element loads.
-template <typename T>
-__device__ __forceinline__ Item load_item(const T* __restrict__ p) {
-  T c[kC];
-  constexpr int kVec = (int)(sizeof(T) * kC / 16);
-  if ((reinterpret_cast<uintptr_t>(p) & 15u) == 0) {
-    uint4 q[kVec];
-#pragma unroll
-    for (int i = 0; i < kVec; ++i) q[i] = reinterpret_cast<const uint4*>(p)[i];
-    __builtin_memcpy(c, q, sizeof(c));
-  } else {
-#pragma unroll
-    for (int i = 0; i < kC; ++i) c[i] = p[i];
-  }
-  Item it;
-  it.type = item_class(c[kTypeCol], kTypes - 1);
-  it.equipped = item_class(c[kEquipCol], 1);
-#pragma unroll
-  for (int k = 0; k < kCont; ++k) it.x[k] = (float)c[cont_col(k)] * kScale;
-  return it;
-}
-
-// SPEC §20's 15-term sum with the head's projected query in LDS
-__device__ __forceinline__ float item_logit(const float* pq, const Item& it) {
-  float v = pq[kF] + pq[it.type];
-  v += pq[kTypes + it.equipped];
-#pragma unroll
-  for (int k = 0; k < kCont; ++k) v = fmaf(pq[kDiscrete + k], it.x[k], v);
-  return v;
-}
-
 // The legal j < m of mask entries mbase + [0, m), ascending, into list[0, cnt); returns cnt
 // (wave-uniform). zero != NULL: zero[j] = 0 for every illegal j < m.
 template <int MK>
@@ -251,14 +204,6 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void nmh_item_logits_kernel(
     }
     wave_sync();  // the next head rebuilds the list
   }
-}
-
-// feature f < 32 of an item from the one column it depends on
-template <typename T>
-__device__ __forceinline__ float item_feature(int f, T c) {
-  if (f < kTypes) return item_class(c, kTypes - 1) == f ? 1.0f : 0.0f;
-  if (f < kDiscrete) return item_class(c, 1) == f - kTypes ? 1.0f : 0.0f;
-  return (float)c * kScale;
 }
 
 template <typename T, int MK>

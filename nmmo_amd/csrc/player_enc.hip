@@ -34,32 +34,24 @@
 
 #include "common.h"
 #include "host_api.h"
+#include "player_dev.h"  // stage_rows, player_logit, feature_col, npc_class: shared with decoder.hip
 #include "../../include/nmmo_heads.h"
 
 using namespace nmmo;
+using namespace nmmo::player_dev;
 
 // heads.hip: the message goes into the error text nmh_last_error() returns
 int heads_record_error(int code, const char* msg);
 
 namespace {
 
-constexpr int kC = NMH_PLAYER_COLS, kF = NMH_PLAYER_FEATURES, kTypes = NMH_PLAYER_TYPES, kQ = NMH_PLAYER_QUERY;
 constexpr int kMaxRows = NMH_PLAYER_MAX_ROWS, kMaxHeads = NMH_PLAYER_MAX_HEADS;
-constexpr int kTypeCol = 1;
-constexpr int kRaw = kC - 2;  // features [6, 35) are columns [2, 31)
 constexpr int kThreads = 256, kSlots = kThreads / kC, kRowsPerBlock = 4, kChunk = 64;
-constexpr int kHeadShift = 12;  // a list entry is j | (the allowing heads' bits << 12)
 
 static_assert(kC == 31 && kF == 35 && kTypes == 5 && kQ == 40 && kRaw == 29 && kSlots == 8, "the start-kit entity row");
 static_assert(kMaxRows <= (1 << kHeadShift) && kMaxHeads <= 16 - kHeadShift, "a list entry is 16 bits");
 
 #define PLAYER_FAIL(code, ...) heads_record_error(fail(code, __VA_ARGS__), g_err.c_str())
-
-// SPEC §21's class rule: clamp(trunc(v), 0, 4), NaN -> 0
-__device__ inline int npc_class(float v) { return v >= 0.0f ? (v >= (float)(kTypes - 1) ? kTypes - 1 : (int)v) : 0; }
-
-// the column feature f < 35 depends on
-__device__ inline int feature_col(int f) { return f == 0 ? 0 : (f <= kTypes ? kTypeCol : f - kTypes + 1); }
 
 // column c's part of x [35]: feature 0, the five one-hots, or feature c + 4
 __device__ inline void put_x(float* __restrict__ x, int c, float v) {
@@ -200,41 +192,6 @@ __device__ __forceinline__ int legal_list(const NmhPlayerHeads& ph, const void* 
     cnt += __popcll(b);
   }
   return cnt;
-}
-
-// The 31 columns of listed candidates [i0, i0 + n) into rows[n][31] as float32: lane e takes
-// element e % 31 of candidate e / 31, so a candidate's 31 elements are consecutive lanes' loads.
-template <typename T>
-__device__ __forceinline__ void stage_rows(const T* __restrict__ set, const uint16_t* list, int i0, int n,
-                                           float* rows) {
-  constexpr int kU = 4;
-  const int tot = n * kC;
-  for (int e0 = lane_id(); e0 < tot; e0 += 64 * kU) {
-    T v[kU];
-#pragma unroll
-    for (int u = 0; u < kU; ++u) {
-      const int e = e0 + 64 * u;
-      v[u] = (T)0;
-      if (e < tot) {
-        const int k = e / kC;
-        v[u] = set[(int64_t)(list[i0 + k] & ((1 << kHeadShift) - 1)) * kC + (e - k * kC)];
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < kU; ++u) {
-      const int e = e0 + 64 * u;
-      if (e < tot) rows[e] = (float)v[u];
-    }
-  }
-}
-
-// SPEC §21's sum of one candidate's LDS row with the head's projected query in LDS
-__device__ __forceinline__ float player_logit(const float* pq, const float* row) {
-  float v = pq[kF] + pq[1 + npc_class(row[kTypeCol])];
-  v = fmaf(pq[0], row[0], v);
-#pragma unroll
-  for (int k = 0; k < kRaw; ++k) v = fmaf(pq[1 + kTypes + k], row[2 + k], v);
-  return v;
 }
 
 template <typename T, int MK>
