@@ -203,11 +203,12 @@ NMH_API int nmh_tile2_backward(int32_t n_rows, const uint8_t* idx, const float* 
 NMH_API int nmh_item_features(int32_t n_sets, const void* items, int64_t item_stride, int32_t item_kind,
                               int32_t set_rows, float* features, float* sums, void* stream);
 
-typedef struct NmhItemHeads { /* 1..NMH_ITEM_MAX_HEADS heads over one item set */
+typedef struct NmhSetHeads { /* 1..NMH_ITEM_MAX_HEADS heads over one candidate set, items or entities */
   int32_t n_heads;
   int32_t mask_off[NMH_ITEM_MAX_HEADS]; /* head h's first of set_rows + 1 entries in a mask row */
   int32_t out_off[NMH_ITEM_MAX_HEADS];  /* ... and in an out / g_out row */
-} NmhItemHeads;
+} NmhSetHeads;
+typedef NmhSetHeads NmhItemHeads; /* 1..NMH_ITEM_MAX_HEADS heads over one item set */
 
 /* Obs row r reads item set r / share (share >= 1: 1 for flat rows, P for the native per-env Market).
  * pq [n_rows, n_heads, 36], 16-byte aligned. out [n_rows, out_stride]. Mask as in nmh_forward; both
@@ -258,11 +259,10 @@ NMH_API int nmh_player_features(int32_t n_sets, const void* ents, int64_t ent_st
                                 int32_t set_rows, const void* ids, int64_t id_stride, int32_t id_kind,
                                 float* features, float* sums, float* mine, int32_t* mine_idx, void* stream);
 
-typedef struct NmhPlayerHeads { /* 1..NMH_PLAYER_MAX_HEADS heads over one entity set */
-  int32_t n_heads;
-  int32_t mask_off[NMH_PLAYER_MAX_HEADS]; /* head h's first of set_rows + 1 entries in a mask row */
-  int32_t out_off[NMH_PLAYER_MAX_HEADS];  /* ... and in an out / g_out row */
-} NmhPlayerHeads;
+#if NMH_ITEM_MAX_HEADS != NMH_PLAYER_MAX_HEADS
+#error "NmhSetHeads serves item and entity sets: NMH_ITEM_MAX_HEADS must equal NMH_PLAYER_MAX_HEADS"
+#endif
+typedef NmhSetHeads NmhPlayerHeads; /* 1..NMH_PLAYER_MAX_HEADS heads over one entity set */
 
 /* Obs row r reads entity set r. pq [n_rows, n_heads, 40], 16-byte aligned. out [n_rows, out_stride].
  * Mask as in nmh_forward; both strides cover the furthest head's set_rows + 1 entries.

@@ -31,15 +31,12 @@
 
 #include "common.h"
 #include "heads_dev.h"
-#include "host_api.h"
+#include "heads_host.h"  // heads_fail, heads_launched, aligned16, check_head_plan
 #include "item_dev.h"
 #include "player_dev.h"
 #include "../../include/nmmo_heads.h"
 
 using namespace nmmo;
-
-// heads.hip: the message goes into the error text nmh_last_error() returns
-int heads_record_error(int code, const char* msg);
 
 namespace {
 
@@ -54,8 +51,6 @@ static_assert(NMH_ITEM_MAX_ROWS < (1 << player_dev::kHeadShift), "stage_rows mas
 static_assert(2 * (NMH_MAX_DIM * 4 + NMH_MAX_HEADS * kSlot * 4 + NMH_PLAYER_MAX_ROWS * 2 + kRowsBytes) <= kMaxLds &&
                   2 * (NMH_MAX_DIM * 4 + NMH_MAX_HEADS * kSlot * 4 + NMH_ITEM_MAX_ROWS * 2) <= kMaxLds,
               "two waves of any accepted shape fit 64 KiB");
-
-#define DEC_FAIL(code, ...) heads_record_error(fail(code, __VA_ARGS__), g_err.c_str())
 
 // what the host works out once per call from NmhHeads + NmhDecoderSets
 struct DecPlan {
@@ -239,41 +234,34 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void nmh_decoder_backward_kerne
   }
 }
 
-int launched(const char* fn) {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? NMH_OK : DEC_FAIL(NMH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
-}
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 // The argument rules both entry points share (SPEC.md §23, "Limits"); fills the plan, *wave_bytes
 // and *dense_total (the dense heads' columns).
 int check_decoder(const char* fn, const NmhHeads* hd, const NmhDecoderSets* st, int32_t n_rows, const float* pq,
                   const float* dense, int64_t ds, const void* mask, int64_t ms, int32_t mask_kind, DecPlan* pl,
                   int* wave_bytes, int64_t* dense_total) {
-  if (!hd) return DEC_FAIL(NMH_E_INVALID, "%s: hd is NULL", fn);
-  if (!st) return DEC_FAIL(NMH_E_INVALID, "%s: sets is NULL", fn);
+  if (!hd) return heads_fail(NMH_E_INVALID, "%s: hd is NULL", fn);
+  if (!st) return heads_fail(NMH_E_INVALID, "%s: sets is NULL", fn);
   if (hd->n_heads < 1 || hd->n_heads > NMH_MAX_HEADS)
-    return DEC_FAIL(NMH_E_INVALID, "%s: n_heads %d outside 1..%d", fn, hd->n_heads, NMH_MAX_HEADS);
+    return heads_fail(NMH_E_INVALID, "%s: n_heads %d outside 1..%d", fn, hd->n_heads, NMH_MAX_HEADS);
   if (st->n_sets < 0 || st->n_sets > NMH_MAX_SETS)
-    return DEC_FAIL(NMH_E_INVALID, "%s: n_sets %d outside 0..%d", fn, st->n_sets, NMH_MAX_SETS);
+    return heads_fail(NMH_E_INVALID, "%s: n_sets %d outside 0..%d", fn, st->n_sets, NMH_MAX_SETS);
   if (st->elem_kind != NMH_ELEM_F32 && st->elem_kind != NMH_ELEM_I16)
-    return DEC_FAIL(NMH_E_INVALID, "%s: unknown elem_kind %d", fn, st->elem_kind);
+    return heads_fail(NMH_E_INVALID, "%s: unknown elem_kind %d", fn, st->elem_kind);
   *pl = DecPlan{};
   int max_item = 0, max_ent = 0;
   for (int s = 0; s < st->n_sets; s++) {
     const int rule = st->rule[s], R = st->set_rows[s];
     if (rule != NMH_SET_ENTITY && rule != NMH_SET_ITEM)
-      return DEC_FAIL(NMH_E_INVALID, "%s: unknown rule[%d] %d", fn, s, rule);
+      return heads_fail(NMH_E_INVALID, "%s: unknown rule[%d] %d", fn, s, rule);
     const int cols = rule == NMH_SET_ITEM ? NMH_ITEM_COLS : NMH_PLAYER_COLS;
     const int max_rows = rule == NMH_SET_ITEM ? NMH_ITEM_MAX_ROWS : NMH_PLAYER_MAX_ROWS;
     if (R < 1 || R > max_rows)
-      return DEC_FAIL(NMH_E_INVALID, "%s: set_rows[%d] = %d outside 1..%d", fn, s, R, max_rows);
-    if (st->share[s] < 1) return DEC_FAIL(NMH_E_INVALID, "%s: share[%d] %d < 1", fn, s, st->share[s]);
+      return heads_fail(NMH_E_INVALID, "%s: set_rows[%d] = %d outside 1..%d", fn, s, R, max_rows);
+    if (st->share[s] < 1) return heads_fail(NMH_E_INVALID, "%s: share[%d] %d < 1", fn, s, st->share[s]);
     if (st->stride[s] < (int64_t)cols * R)
-      return DEC_FAIL(NMH_E_INVALID, "%s: stride[%d] %lld < %d set_rows = %d", fn, s, (long long)st->stride[s], cols,
-                      cols * R);
-    if (!st->base[s]) return DEC_FAIL(NMH_E_INVALID, "%s: base[%d] is NULL", fn, s);
+      return heads_fail(NMH_E_INVALID, "%s: stride[%d] %lld < %d set_rows = %d", fn, s, (long long)st->stride[s], cols,
+                        cols * R);
+    if (!st->base[s]) return heads_fail(NMH_E_INVALID, "%s: base[%d] is NULL", fn, s);
     if (rule == NMH_SET_ITEM) max_item = std::max(max_item, R);
     else max_ent = std::max(max_ent, R);
     pl->rule[s] = rule;
@@ -281,54 +269,20 @@ int check_decoder(const char* fn, const NmhHeads* hd, const NmhDecoderSets* st, 
     pl->stride[s] = st->stride[s];
     pl->base[s] = st->base[s];
   }
-  pl->n_heads = hd->n_heads;
-  int64_t sum = 0, dsum = 0;
-  unsigned used = 0;
-  for (int k = 0; k < hd->n_heads; k++) {
-    const int n = hd->dims[k], s = st->head_set[k];
-    if (n < 1 || n > NMH_MAX_DIM)
-      return DEC_FAIL(NMH_E_INVALID, "%s: dims[%d] = %d outside 1..%d", fn, k, n, NMH_MAX_DIM);
-    if (s < -1 || s >= st->n_sets)
-      return DEC_FAIL(NMH_E_INVALID, "%s: head_set[%d] = %d outside -1..%d", fn, k, s, st->n_sets - 1);
-    if (s >= 0 && n != st->set_rows[s] + 1)
-      return DEC_FAIL(NMH_E_INVALID, "%s: dims[%d] = %d is not set_rows[%d] + 1 = %d", fn, k, n, s,
-                      st->set_rows[s] + 1);
-    pl->dims[k] = n;
-    pl->off[k] = (int32_t)sum;
-    pl->set[k] = s;
-    if (s < 0) {
-      pl->src[k] = (int32_t)dsum;
-      dsum += n;
-    } else {
-      pl->src[k] = pl->n_ptr++;
-      used |= 1u << s;
-    }
-    sum += n;
-  }
-  if (sum > NMH_MAX_DIM)
-    return DEC_FAIL(NMH_E_INVALID, "%s: sum(dims) %lld exceeds NMH_MAX_DIM %d", fn, (long long)sum, NMH_MAX_DIM);
-  for (int s = 0; s < st->n_sets; s++)
-    if (!(used >> s & 1u)) return DEC_FAIL(NMH_E_INVALID, "%s: no head uses set %d (head_set)", fn, s);
-  if (n_rows < 0) return DEC_FAIL(NMH_E_INVALID, "%s: n_rows %d is negative", fn, n_rows);
-  if (!mask) return DEC_FAIL(NMH_E_INVALID, "%s: mask is NULL", fn);
-  if (mask_kind != NMH_MASK_F32 && mask_kind != NMH_MASK_U8)
-    return DEC_FAIL(NMH_E_INVALID, "%s: unknown mask_kind %d", fn, mask_kind);
-  if (ms < sum)
-    return DEC_FAIL(NMH_E_INVALID, "%s: mask_stride %lld < sum(dims) %lld", fn, (long long)ms, (long long)sum);
-  if (dsum > 0 && !dense) return DEC_FAIL(NMH_E_INVALID, "%s: dense is NULL with dense heads", fn);
-  if (dsum > 0 && ds < dsum)
-    return DEC_FAIL(NMH_E_INVALID, "%s: dense_stride %lld < the dense heads' %lld columns", fn, (long long)ds,
-                    (long long)dsum);
+  int64_t sum;
+  const int rc = check_head_plan(fn, hd, st->n_sets, st->set_rows, st->head_set, "set", n_rows, dense, ds, mask, ms,
+                                 mask_kind, {&pl->n_heads, &pl->n_ptr, pl->dims, pl->off, pl->set, pl->src}, &sum,
+                                 dense_total);
+  if (rc != NMH_OK) return rc;
   if (pl->n_ptr > 0) {
-    if (!pq) return DEC_FAIL(NMH_E_INVALID, "%s: pq is NULL with pointer heads", fn);
-    if (!aligned16(pq)) return DEC_FAIL(NMH_E_INVALID, "%s: pq is not 16-byte aligned", fn);
+    if (!pq) return heads_fail(NMH_E_INVALID, "%s: pq is NULL with pointer heads", fn);
+    if (!aligned16(pq)) return heads_fail(NMH_E_INVALID, "%s: pq is not 16-byte aligned", fn);
   }
   pl->total = (int32_t)sum;
   pl->u_off = (int32_t)(sum * 4 + pl->n_ptr * kSlot * 4);
   pl->rows_off = (max_ent * 2 + 3) & ~3;
   const int u_bytes = std::max(max_item * 2, max_ent ? pl->rows_off + kRowsBytes : 0);
   *wave_bytes = (pl->u_off + u_bytes + 15) & ~15;
-  *dense_total = dsum;
   return NMH_OK;
 }
 
@@ -361,12 +315,12 @@ int nmh_decoder_forward(const NmhHeads* hd, const NmhDecoderSets* st, int32_t n_
                                &wave_bytes, &dense_total);
   if (rc != NMH_OK) return rc;
   if (!actions_out || !logprob || !entropy || !lse || !head_entropy)
-    return DEC_FAIL(NMH_E_INVALID, "%s: an output pointer is NULL", fn);
+    return heads_fail(NMH_E_INVALID, "%s: an output pointer is NULL", fn);
   if (n_rows == 0) return NMH_OK;
   DEC_LAUNCH(nmh_decoder_forward_kernel, pq, dense, dense_stride, mask, mask_stride, actions_in, (uint32_t)seed,
              (uint32_t)(seed >> 32), (uint32_t)offset, (uint32_t)(offset >> 32), row_base, actions_out, logprob,
              entropy, lse, head_entropy);
-  return launched(fn);
+  return heads_launched(fn);
 }
 
 int nmh_decoder_backward(const NmhHeads* hd, const NmhDecoderSets* st, int32_t n_rows, const float* pq,
@@ -382,17 +336,17 @@ int nmh_decoder_backward(const NmhHeads* hd, const NmhDecoderSets* st, int32_t n
                                &wave_bytes, &dense_total);
   if (rc != NMH_OK) return rc;
   if (!actions || !lse || !head_entropy)
-    return DEC_FAIL(NMH_E_INVALID, "%s: actions, lse or head_entropy is NULL", fn);
+    return heads_fail(NMH_E_INVALID, "%s: actions, lse or head_entropy is NULL", fn);
   if (g_dense && g_dense_stride < dense_total)
-    return DEC_FAIL(NMH_E_INVALID, "%s: g_dense_stride %lld < the dense heads' %lld columns", fn,
-                    (long long)g_dense_stride, (long long)dense_total);
-  if (g_pq && !aligned16(g_pq)) return DEC_FAIL(NMH_E_INVALID, "%s: g_pq is not 16-byte aligned", fn);
+    return heads_fail(NMH_E_INVALID, "%s: g_dense_stride %lld < the dense heads' %lld columns", fn,
+                      (long long)g_dense_stride, (long long)dense_total);
+  if (g_pq && !aligned16(g_pq)) return heads_fail(NMH_E_INVALID, "%s: g_pq is not 16-byte aligned", fn);
   if (dense_total == 0) g_dense = nullptr;
   if (pl.n_ptr == 0) g_pq = nullptr;
   if (n_rows == 0 || (!g_dense && !g_pq)) return NMH_OK;
   DEC_LAUNCH(nmh_decoder_backward_kernel, pq, dense, dense_stride, mask, mask_stride, actions, lse, head_entropy,
              g_logprob, g_entropy, g_dense, g_dense_stride, g_pq);
-  return launched(fn);
+  return heads_launched(fn);
 }
 
 }  // extern "C"

@@ -20,7 +20,8 @@
 
 #include "common.h"
 #include "heads_dev.h"  // head_forward, tile_heads, legal_list, wave_sync: shared with decoder.hip
-#include "host_api.h"
+#include "heads_host.h"
+#include "host_api.h"  // g_err and fail(): the library's one error text lives in this translation unit
 #include "../../include/nmmo_heads.h"
 
 using namespace nmmo;
@@ -359,13 +360,6 @@ int check_args(const char* fn, const NmhHeads* hd, int32_t n_rows, const void* l
   return NMH_OK;
 }
 
-int launched(const char* fn) {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? NMH_OK : fail(NMH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
-}
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // The argument checks the two pointer entry points share (SPEC.md §18, "Limits"); fills the plan,
 // *dense_total (the dense heads' columns) and *max_rows (the largest set_rows in use).
 int check_pointer(const char* fn, const NmhHeads* hd, const NmhPointer* pt, int32_t n_rows, const float* queries,
@@ -380,49 +374,19 @@ int check_pointer(const char* fn, const NmhHeads* hd, const NmhPointer* pt, int3
   const int D = pt->key_dim;
   if (pt->n_sets > 0 && (D < 4 || D > NMH_MAX_KEY_DIM || D % 4))
     return fail(NMH_E_INVALID, "%s: key_dim %d is not a multiple of 4 in 4..%d", fn, D, NMH_MAX_KEY_DIM);
-  for (int s = 0; s < pt->n_sets; s++)
+  *max_rows = 0;  // every set is in use once the plan stands
+  for (int s = 0; s < pt->n_sets; s++) {
     if (pt->set_rows[s] < 1 || pt->set_rows[s] >= NMH_MAX_DIM)
       return fail(NMH_E_INVALID, "%s: set_rows[%d] = %d outside 1..%d", fn, s, pt->set_rows[s], NMH_MAX_DIM - 1);
+    *max_rows = std::max(*max_rows, pt->set_rows[s]);
+  }
   *pl = PtrPlan{};
-  pl->n_heads = hd->n_heads;
   pl->n_sets = pt->n_sets;
   pl->key_dim = D;
-  int64_t sum = 0, dsum = 0;
-  unsigned used = 0;
-  *max_rows = 0;
-  for (int k = 0; k < hd->n_heads; k++) {
-    const int n = hd->dims[k], s = pt->head_set[k];
-    if (n < 1 || n > NMH_MAX_DIM)
-      return fail(NMH_E_INVALID, "%s: dims[%d] = %d outside 1..%d", fn, k, n, NMH_MAX_DIM);
-    if (s < -1 || s >= pt->n_sets)
-      return fail(NMH_E_INVALID, "%s: head_set[%d] = %d outside -1..%d", fn, k, s, pt->n_sets - 1);
-    if (s >= 0 && n != pt->set_rows[s] + 1)
-      return fail(NMH_E_INVALID, "%s: dims[%d] = %d is not set_rows[%d] + 1 = %d", fn, k, n, s, pt->set_rows[s] + 1);
-    pl->dims[k] = n;
-    pl->off[k] = (int32_t)sum;
-    pl->set[k] = s;
-    if (s < 0) {
-      pl->src[k] = (int32_t)dsum;
-      dsum += n;
-    } else {
-      pl->src[k] = pl->n_ptr++;
-      used |= 1u << s;
-      *max_rows = std::max(*max_rows, n - 1);
-    }
-    sum += n;
-  }
-  if (sum > NMH_MAX_DIM)
-    return fail(NMH_E_INVALID, "%s: sum(dims) %lld exceeds NMH_MAX_DIM %d", fn, (long long)sum, NMH_MAX_DIM);
-  for (int s = 0; s < pt->n_sets; s++)
-    if (!(used >> s & 1u)) return fail(NMH_E_INVALID, "%s: no head uses key set %d (head_set)", fn, s);
-  if (n_rows < 0) return fail(NMH_E_INVALID, "%s: n_rows %d is negative", fn, n_rows);
-  if (!mask) return fail(NMH_E_INVALID, "%s: mask is NULL", fn);
-  if (mask_kind != NMH_MASK_F32 && mask_kind != NMH_MASK_U8)
-    return fail(NMH_E_INVALID, "%s: unknown mask_kind %d", fn, mask_kind);
-  if (ms < sum) return fail(NMH_E_INVALID, "%s: mask_stride %lld < sum(dims) %lld", fn, (long long)ms, (long long)sum);
-  if (dsum > 0 && !dense) return fail(NMH_E_INVALID, "%s: dense is NULL with dense heads", fn);
-  if (dsum > 0 && ds < dsum)
-    return fail(NMH_E_INVALID, "%s: dense_stride %lld < the dense heads' %lld columns", fn, (long long)ds, (long long)dsum);
+  const int rc = check_head_plan(fn, hd, pt->n_sets, pt->set_rows, pt->head_set, "key set", n_rows, dense, ds, mask, ms,
+                                 mask_kind, {&pl->n_heads, &pl->n_ptr, pl->dims, pl->off, pl->set, pl->src}, total,
+                                 dense_total);
+  if (rc != NMH_OK) return rc;
   if (pl->n_ptr > 0) {
     if (!queries || !keys) return fail(NMH_E_INVALID, "%s: queries or keys is NULL with pointer heads", fn);
     if (!aligned16(queries)) return fail(NMH_E_INVALID, "%s: queries is not 16-byte aligned", fn);
@@ -433,8 +397,6 @@ int check_pointer(const char* fn, const NmhHeads* hd, const NmhPointer* pt, int3
       pl->keys[s] = keys[s];
     }
   }
-  *total = sum;
-  *dense_total = dsum;
   return NMH_OK;
 }
 
@@ -449,14 +411,26 @@ int check_pointer(const char* fn, const NmhHeads* hd, const NmhPointer* pt, int3
                            : (f32 ? K<NMH_MASK_F32, 4> : K<NMH_MASK_U8, 4>);                                     \
     hipLaunchKernelGGL(kern, grid, block, (size_t)kRowsPerBlock* wave_bytes, static_cast<hipStream_t>(stream), pl, \
                        n_rows, (int)total, wave_bytes, __VA_ARGS__);                                             \
-    return launched(fn);                                                                                         \
+    return heads_launched(fn);                                                                                   \
   } while (0)
 
 }  // namespace
 
-// For the library's other translation unit (tile_enc.hip), whose copy of host_api.h's g_err is not
-// the one nmh_last_error() reads. Hidden visibility: not an export.
-int heads_record_error(int code, const char* msg) { return fail(code, "%s", msg); }
+// heads_host.h: the library's other translation units report through these two, so that every
+// message lands in the g_err nmh_last_error() reads.
+int heads_fail(int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  return fail(code, "%s", buf);
+}
+
+int heads_launched(const char* fn) {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? NMH_OK : fail(NMH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
+}
 
 extern "C" {
 
@@ -479,7 +453,7 @@ int nmh_forward(const NmhHeads* hd, int32_t n_rows, const float* logits, int64_t
   hipLaunchKernelGGL(kern, grid, block, sizeof(float) * kRowsPerBlock * tile, static_cast<hipStream_t>(stream), *hd,
                      n_rows, tile, logits, logits_stride, mask, mask_stride, actions_in, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)offset,
                      (uint32_t)(offset >> 32), row_base, actions_out, logprob, entropy, lse, head_entropy);
-  return launched("nmh_forward");
+  return heads_launched("nmh_forward");
 }
 
 int nmh_backward(const NmhHeads* hd, int32_t n_rows, const float* logits, int64_t logits_stride, const void* mask,
@@ -498,7 +472,7 @@ int nmh_backward(const NmhHeads* hd, int32_t n_rows, const float* logits, int64_
   auto* kern = mask_kind == NMH_MASK_F32 ? nmh_backward_kernel<NMH_MASK_F32> : nmh_backward_kernel<NMH_MASK_U8>;
   hipLaunchKernelGGL(kern, grid, block, 0, static_cast<hipStream_t>(stream), *hd, n_rows, logits, logits_stride, mask,
                      mask_stride, actions, lse, head_entropy, g_logprob, g_entropy, g_logits, g_stride);
-  return launched("nmh_backward");
+  return heads_launched("nmh_backward");
 }
 
 int nmh_pointer_forward(const NmhHeads* hd, const NmhPointer* pt, int32_t n_rows, const float* queries,

@@ -1,6 +1,7 @@
 // heads_dev.h — the device functions of the masked heads that more than one translation unit of
-// libnmmo_heads.so uses (heads.hip, decoder.hip): the float wave reductions, one head of one row on
-// one wave from its staged tile (SPEC.md §15), the heads of a tile in sequence, and the legal list
+// libnmmo_heads.so uses: wave_sync and legal_at (heads.hip, decoder.hip, item_enc.hip,
+// player_enc.hip) and, for heads.hip and decoder.hip, the float wave reductions, one head of one row
+// on one wave from its staged tile (SPEC.md §15), the heads of a tile in sequence, and the legal list
 // of a pointer head (SPEC.md §18). Internal linkage: every translation unit compiles its own copy.
 #pragma once
 

@@ -28,15 +28,13 @@
 #include <stdint.h>
 
 #include "common.h"
-#include "host_api.h"
-#include "item_dev.h"  // load_item, item_logit, item_feature, item_class: shared with decoder.hip
+#include "heads_dev.h"   // wave_sync, legal_at
+#include "heads_host.h"  // heads_fail, heads_launched, aligned16, check_set, check_logits, HEADS_SET_LAUNCH
+#include "item_dev.h"    // load_item, item_logit, item_feature, item_class: shared with decoder.hip
 #include "../../include/nmmo_heads.h"
 
 using namespace nmmo;
 using namespace nmmo::item_dev;
-
-// heads.hip: the message goes into the error text nmh_last_error() returns
-int heads_record_error(int code, const char* msg);
 
 namespace {
 
@@ -45,23 +43,9 @@ constexpr int kThreads = 256, kRowsPerBlock = 4;
 
 static_assert(kC == 16 && kF == 32 && kTypes == 18 && kQ == 36 && kCont == 12, "the start-kit item row");
 
-#define ITEM_FAIL(code, ...) heads_record_error(fail(code, __VA_ARGS__), g_err.c_str())
-
 // lane `src`'s value of v (every lane of the wave takes part)
 __device__ inline float shfl_item(float v, int src) { return __shfl(v, src); }
 __device__ inline int16_t shfl_item(int16_t v, int src) { return (int16_t)__shfl((int)v, src); }
-
-__device__ __forceinline__ void wave_sync() {  // this wave's LDS stores before its later LDS loads
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-template <int MK>
-__device__ __forceinline__ bool legal_at(const void* mask, int64_t i) {
-  if (MK == NMH_MASK_F32) return static_cast<const float*>(mask)[i] > 0.f;
-  return static_cast<const uint8_t*>(mask)[i] != 0;
-}
 
 // ---------------------------------------------------------------- features and sums
 // G threads per set: 64 (a wave; R <= 64) or 256 (the workgroup).
@@ -134,10 +118,11 @@ __global__ __launch_bounds__(kThreads) void nmh_item_features_kernel(
 
 // ---------------------------------------------------------------- pointer logits
 // The legal j < m of mask entries mbase + [0, m), ascending, into list[0, cnt); returns cnt
-// (wave-uniform). zero != NULL: zero[j] = 0 for every illegal j < m.
+// (wave-uniform). zero != NULL: zero[j] = 0 for every illegal j < m. (heads_dev.h's legal_list fills
+// an LDS tile's every entry; this one stores to a global row, and only where the mask forbids.)
 template <int MK>
-__device__ __forceinline__ int legal_list(const void* __restrict__ mask, int64_t mbase, int m, uint16_t* list,
-                                          float* __restrict__ zero) {
+__device__ __forceinline__ int item_legal_list(const void* __restrict__ mask, int64_t mbase, int m, uint16_t* list,
+                                               float* __restrict__ zero) {
   constexpr int kU = 4;  // mask loads in flight per lane
   int cnt = 0;
   for (int b0 = 0; b0 < m; b0 += 64 * kU) {  // (wave-uniform trip count: every lane ballots)
@@ -195,7 +180,7 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void nmh_item_logits_kernel(
   }
   for (int h = 0; h < H; ++h) {
     float* __restrict__ oh = orow + ih.out_off[h];
-    const int cnt = legal_list<MK>(mask, r * ms + ih.mask_off[h], R, list, oh);
+    const int cnt = item_legal_list<MK>(mask, r * ms + ih.mask_off[h], R, list, oh);
     if (lane == 0) oh[R] = 0.0f;  // the no-op entry
     wave_sync();
     for (int i = lane; i < cnt; i += 64) {
@@ -222,7 +207,7 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void nmh_item_logits_backward_k
   const int col = f < kTypes ? kTypeCol : (f < kDiscrete ? kEquipCol : cont_col(min(f, kF - 1) - kDiscrete));
   for (int h = 0; h < H; ++h) {
     const float* __restrict__ gh = g_out + r * gs + ih.out_off[h];
-    const int cnt = legal_list<MK>(mask, r * ms + ih.mask_off[h], R, list, nullptr);
+    const int cnt = item_legal_list<MK>(mask, r * ms + ih.mask_off[h], R, list, nullptr);
     wave_sync();
     float acc = 0.0f;
     if (f <= kF) {
@@ -249,54 +234,6 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void nmh_item_logits_backward_k
   }
 }
 
-int launched(const char* fn) {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? NMH_OK : ITEM_FAIL(NMH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
-}
-
-int check_set(const char* fn, const void* items, int64_t item_stride, int32_t item_kind, int32_t set_rows) {
-  if (!items) return ITEM_FAIL(NMH_E_INVALID, "%s: items is NULL", fn);
-  if (item_kind != NMH_ITEM_F32 && item_kind != NMH_ITEM_I16)
-    return ITEM_FAIL(NMH_E_INVALID, "%s: unknown item_kind %d", fn, item_kind);
-  if (set_rows < 1 || set_rows > kMaxRows)
-    return ITEM_FAIL(NMH_E_INVALID, "%s: set_rows %d outside 1..%d", fn, set_rows, kMaxRows);
-  if (item_stride < (int64_t)kC * set_rows)
-    return ITEM_FAIL(NMH_E_INVALID, "%s: item_stride %lld < %d set_rows = %d", fn, (long long)item_stride, kC,
-                     kC * set_rows);
-  return NMH_OK;
-}
-
-// the rules nmh_item_logits and its backward share; `out` names the [n_rows, out_stride] argument
-int check_logits(const char* fn, const NmhItemHeads* ih, int32_t n_rows, const void* items, int64_t item_stride,
-                 int32_t item_kind, int32_t set_rows, int32_t share, const void* mask, int64_t mask_stride,
-                 int32_t mask_kind, const char* out_name, const void* out, const char* stride_name, int64_t out_stride) {
-  if (!ih) return ITEM_FAIL(NMH_E_INVALID, "%s: ih is NULL", fn);
-  if (n_rows < 0) return ITEM_FAIL(NMH_E_INVALID, "%s: n_rows %d is negative", fn, n_rows);
-  if (ih->n_heads < 1 || ih->n_heads > kMaxHeads)
-    return ITEM_FAIL(NMH_E_INVALID, "%s: n_heads %d outside 1..%d", fn, ih->n_heads, kMaxHeads);
-  const int rc = check_set(fn, items, item_stride, item_kind, set_rows);
-  if (rc != NMH_OK) return rc;
-  if (share < 1) return ITEM_FAIL(NMH_E_INVALID, "%s: share %d < 1", fn, share);
-  if (!mask) return ITEM_FAIL(NMH_E_INVALID, "%s: mask is NULL", fn);
-  if (mask_kind != NMH_MASK_F32 && mask_kind != NMH_MASK_U8)
-    return ITEM_FAIL(NMH_E_INVALID, "%s: unknown mask_kind %d", fn, mask_kind);
-  if (!out) return ITEM_FAIL(NMH_E_INVALID, "%s: %s is NULL", fn, out_name);
-  for (int h = 0; h < ih->n_heads; ++h) {
-    if (ih->mask_off[h] < 0 || ih->out_off[h] < 0)
-      return ITEM_FAIL(NMH_E_INVALID, "%s: mask_off[%d] %d or out_off[%d] %d is negative", fn, h, ih->mask_off[h], h,
-                       ih->out_off[h]);
-    if (mask_stride < (int64_t)ih->mask_off[h] + set_rows + 1)
-      return ITEM_FAIL(NMH_E_INVALID, "%s: mask_stride %lld < mask_off[%d] + set_rows + 1 = %lld", fn,
-                       (long long)mask_stride, h, (long long)ih->mask_off[h] + set_rows + 1);
-    if (out_stride < (int64_t)ih->out_off[h] + set_rows + 1)
-      return ITEM_FAIL(NMH_E_INVALID, "%s: %s %lld < out_off[%d] + set_rows + 1 = %lld", fn, stride_name,
-                       (long long)out_stride, h, (long long)ih->out_off[h] + set_rows + 1);
-  }
-  return NMH_OK;
-}
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace
 
 extern "C" {
@@ -304,10 +241,10 @@ extern "C" {
 int nmh_item_features(int32_t n_sets, const void* items, int64_t item_stride, int32_t item_kind, int32_t set_rows,
                       float* features, float* sums, void* stream) {
   const char* fn = "nmh_item_features";
-  if (n_sets < 0) return ITEM_FAIL(NMH_E_INVALID, "%s: n_sets %d is negative", fn, n_sets);
-  const int rc = check_set(fn, items, item_stride, item_kind, set_rows);
+  if (n_sets < 0) return heads_fail(NMH_E_INVALID, "%s: n_sets %d is negative", fn, n_sets);
+  const int rc = check_set(fn, kItemSets, items, item_stride, item_kind, set_rows);
   if (rc != NMH_OK) return rc;
-  if (!features && !sums) return ITEM_FAIL(NMH_E_INVALID, "%s: features and sums are both NULL", fn);
+  if (!features && !sums) return heads_fail(NMH_E_INVALID, "%s: features and sums are both NULL", fn);
   if (n_sets == 0) return NMH_OK;
   const bool small = set_rows <= 64, f32 = item_kind == NMH_ITEM_F32;
   const int per_block = small ? kThreads / 64 : 1;
@@ -321,35 +258,22 @@ int nmh_item_features(int32_t n_sets, const void* items, int64_t item_stride, in
   else if (small) ITEM_FEATURES(int16_t, 64);
   else ITEM_FEATURES(int16_t, 256);
 #undef ITEM_FEATURES
-  return launched(fn);
+  return heads_launched(fn);
 }
-
-#define ITEM_LAUNCH(K, ...)                                                                               \
-  do {                                                                                                    \
-    const dim3 grid((unsigned)((n_rows + kRowsPerBlock - 1) / kRowsPerBlock)), block(64 * kRowsPerBlock); \
-    hipStream_t st = static_cast<hipStream_t>(stream);                                                    \
-    const bool mf = mask_kind == NMH_MASK_F32;                                                            \
-    if (item_kind == NMH_ITEM_F32) {                                                                      \
-      auto* kern = mf ? K<float, NMH_MASK_F32> : K<float, NMH_MASK_U8>;                                   \
-      hipLaunchKernelGGL(kern, grid, block, 0, st, *ih, n_rows, static_cast<const float*>(items), __VA_ARGS__);   \
-    } else {                                                                                              \
-      auto* kern = mf ? K<int16_t, NMH_MASK_F32> : K<int16_t, NMH_MASK_U8>;                               \
-      hipLaunchKernelGGL(kern, grid, block, 0, st, *ih, n_rows, static_cast<const int16_t*>(items), __VA_ARGS__); \
-    }                                                                                                     \
-  } while (0)
 
 int nmh_item_logits(const NmhItemHeads* ih, int32_t n_rows, const void* items, int64_t item_stride, int32_t item_kind,
                     int32_t set_rows, int32_t share, const void* mask, int64_t mask_stride, int32_t mask_kind,
                     const float* pq, float* out, int64_t out_stride, void* stream) {
   const char* fn = "nmh_item_logits";
-  const int rc = check_logits(fn, ih, n_rows, items, item_stride, item_kind, set_rows, share, mask, mask_stride,
-                              mask_kind, "out", out, "out_stride", out_stride);
+  const int rc = check_logits(fn, kItemSets, ih, n_rows, items, item_stride, item_kind, set_rows, share, mask,
+                              mask_stride, mask_kind, "out", out, "out_stride", out_stride);
   if (rc != NMH_OK) return rc;
-  if (!pq) return ITEM_FAIL(NMH_E_INVALID, "%s: pq is NULL", fn);
-  if (!aligned16(pq)) return ITEM_FAIL(NMH_E_INVALID, "%s: pq is not 16-byte aligned", fn);
+  if (!pq) return heads_fail(NMH_E_INVALID, "%s: pq is NULL", fn);
+  if (!aligned16(pq)) return heads_fail(NMH_E_INVALID, "%s: pq is not 16-byte aligned", fn);
   if (n_rows == 0) return NMH_OK;
-  ITEM_LAUNCH(nmh_item_logits_kernel, item_stride, set_rows, share, mask, mask_stride, pq, out, out_stride);
-  return launched(fn);
+  HEADS_SET_LAUNCH(nmh_item_logits_kernel, item_kind, mask_kind, kRowsPerBlock, stream, ih, n_rows, items, item_stride,
+                   set_rows, share, mask, mask_stride, pq, out, out_stride);
+  return heads_launched(fn);
 }
 
 int nmh_item_logits_backward(const NmhItemHeads* ih, int32_t n_rows, const void* items, int64_t item_stride,
@@ -357,15 +281,14 @@ int nmh_item_logits_backward(const NmhItemHeads* ih, int32_t n_rows, const void*
                              int64_t mask_stride, int32_t mask_kind, const float* g_out, int64_t g_stride,
                              float* g_pq, void* stream) {
   const char* fn = "nmh_item_logits_backward";
-  const int rc = check_logits(fn, ih, n_rows, items, item_stride, item_kind, set_rows, share, mask, mask_stride,
-                              mask_kind, "g_out", g_out, "g_stride", g_stride);
+  const int rc = check_logits(fn, kItemSets, ih, n_rows, items, item_stride, item_kind, set_rows, share, mask,
+                              mask_stride, mask_kind, "g_out", g_out, "g_stride", g_stride);
   if (rc != NMH_OK) return rc;
-  if (!g_pq) return ITEM_FAIL(NMH_E_INVALID, "%s: g_pq is NULL", fn);
+  if (!g_pq) return heads_fail(NMH_E_INVALID, "%s: g_pq is NULL", fn);
   if (n_rows == 0) return NMH_OK;
-  ITEM_LAUNCH(nmh_item_logits_backward_kernel, item_stride, set_rows, share, mask, mask_stride, g_out, g_stride, g_pq);
-  return launched(fn);
+  HEADS_SET_LAUNCH(nmh_item_logits_backward_kernel, item_kind, mask_kind, kRowsPerBlock, stream, ih, n_rows, items,
+                   item_stride, set_rows, share, mask, mask_stride, g_out, g_stride, g_pq);
+  return heads_launched(fn);
 }
-
-#undef ITEM_LAUNCH
 
 }  // extern "C"

@@ -33,15 +33,13 @@
 #include <stdint.h>
 
 #include "common.h"
-#include "host_api.h"
+#include "heads_dev.h"   // wave_sync, legal_at
+#include "heads_host.h"  // heads_fail, heads_launched, aligned16, check_set, check_logits, HEADS_SET_LAUNCH
 #include "player_dev.h"  // stage_rows, player_logit, feature_col, npc_class: shared with decoder.hip
 #include "../../include/nmmo_heads.h"
 
 using namespace nmmo;
 using namespace nmmo::player_dev;
-
-// heads.hip: the message goes into the error text nmh_last_error() returns
-int heads_record_error(int code, const char* msg);
 
 namespace {
 
@@ -50,8 +48,6 @@ constexpr int kThreads = 256, kSlots = kThreads / kC, kRowsPerBlock = 4, kChunk 
 
 static_assert(kC == 31 && kF == 35 && kTypes == 5 && kQ == 40 && kRaw == 29 && kSlots == 8, "the start-kit entity row");
 static_assert(kMaxRows <= (1 << kHeadShift) && kMaxHeads <= 16 - kHeadShift, "a list entry is 16 bits");
-
-#define PLAYER_FAIL(code, ...) heads_record_error(fail(code, __VA_ARGS__), g_err.c_str())
 
 // column c's part of x [35]: feature 0, the five one-hots, or feature c + 4
 __device__ inline void put_x(float* __restrict__ x, int c, float v) {
@@ -66,18 +62,6 @@ __device__ inline void put_x(float* __restrict__ x, int c, float v) {
 
 __device__ inline float load_id(const void* __restrict__ ids, int64_t i, int id_kind) {
   return id_kind == NMH_PLAYER_F32 ? static_cast<const float*>(ids)[i] : (float)static_cast<const int16_t*>(ids)[i];
-}
-
-__device__ __forceinline__ void wave_sync() {  // this wave's LDS stores before its later LDS loads
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-template <int MK>
-__device__ __forceinline__ bool legal_at(const void* mask, int64_t i) {
-  if (MK == NMH_MASK_F32) return static_cast<const float*>(mask)[i] > 0.f;
-  return static_cast<const uint8_t*>(mask)[i] != 0;
 }
 
 // ---------------------------------------------------------------- features, sums and the own row
@@ -169,8 +153,8 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void nmh_player_own_kernel(
 // The j < R that any head allows, ascending, into list[0, cnt) as j | heads << 12; returns cnt
 // (wave-uniform). ZERO: orow[out_off[h] + j] = 0 for every j < R head h forbids.
 template <int MK, bool ZERO>
-__device__ __forceinline__ int legal_list(const NmhPlayerHeads& ph, const void* __restrict__ mask, int64_t mbase, int R,
-                                          uint16_t* list, float* __restrict__ orow) {
+__device__ __forceinline__ int player_legal_list(const NmhPlayerHeads& ph, const void* __restrict__ mask, int64_t mbase,
+                                                 int R, uint16_t* list, float* __restrict__ orow) {
   const int H = ph.n_heads, lane = lane_id();
   int cnt = 0;
   for (int b0 = 0; b0 < R; b0 += 64) {  // (wave-uniform trip count: every lane ballots)
@@ -211,7 +195,7 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void nmh_player_logits_kernel(
   for (int i = lane; i < H * kQ; i += 64) spq[i] = pq[r * H * kQ + i];
   const T* __restrict__ set = ents + r * ent_stride;
   float* __restrict__ orow = out + r * os;
-  const int cnt = legal_list<MK, true>(ph, mask, r * ms, R, list, orow);
+  const int cnt = player_legal_list<MK, true>(ph, mask, r * ms, R, list, orow);
 #pragma unroll
   for (int h = 0; h < kMaxHeads; ++h)
     if (h < H && lane == h) orow[ph.out_off[h] + R] = 0.0f;  // the no-op entries
@@ -246,7 +230,7 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void nmh_player_logits_backward
   uint16_t* list = s_list[w];
   const T* __restrict__ set = ents + r * ent_stride;
   const float* __restrict__ grow = g_out + r * gs;
-  const int cnt = legal_list<MK, false>(ph, mask, r * ms, R, list, nullptr);
+  const int cnt = player_legal_list<MK, false>(ph, mask, r * ms, R, list, nullptr);
   // the column feature f reads; the constant (f = 35) and the lanes beyond read column 0 and drop it
   const int col = f < kF ? feature_col(f) : 0;
   float acc[kMaxHeads] = {};
@@ -282,53 +266,6 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void nmh_player_logits_backward
   }
 }
 
-int launched(const char* fn) {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? NMH_OK : PLAYER_FAIL(NMH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
-}
-
-int check_set(const char* fn, const void* ents, int64_t ent_stride, int32_t ent_kind, int32_t set_rows) {
-  if (!ents) return PLAYER_FAIL(NMH_E_INVALID, "%s: ents is NULL", fn);
-  if (ent_kind != NMH_PLAYER_F32 && ent_kind != NMH_PLAYER_I16)
-    return PLAYER_FAIL(NMH_E_INVALID, "%s: unknown ent_kind %d", fn, ent_kind);
-  if (set_rows < 1 || set_rows > kMaxRows)
-    return PLAYER_FAIL(NMH_E_INVALID, "%s: set_rows %d outside 1..%d", fn, set_rows, kMaxRows);
-  if (ent_stride < (int64_t)kC * set_rows)
-    return PLAYER_FAIL(NMH_E_INVALID, "%s: ent_stride %lld < %d set_rows = %d", fn, (long long)ent_stride, kC,
-                       kC * set_rows);
-  return NMH_OK;
-}
-
-// the rules nmh_player_logits and its backward share; `out` names the [n_rows, out_stride] argument
-int check_logits(const char* fn, const NmhPlayerHeads* ph, int32_t n_rows, const void* ents, int64_t ent_stride,
-                 int32_t ent_kind, int32_t set_rows, const void* mask, int64_t mask_stride, int32_t mask_kind,
-                 const char* out_name, const void* out, const char* stride_name, int64_t out_stride) {
-  if (!ph) return PLAYER_FAIL(NMH_E_INVALID, "%s: ph is NULL", fn);
-  if (n_rows < 0) return PLAYER_FAIL(NMH_E_INVALID, "%s: n_rows %d is negative", fn, n_rows);
-  if (ph->n_heads < 1 || ph->n_heads > kMaxHeads)
-    return PLAYER_FAIL(NMH_E_INVALID, "%s: n_heads %d outside 1..%d", fn, ph->n_heads, kMaxHeads);
-  const int rc = check_set(fn, ents, ent_stride, ent_kind, set_rows);
-  if (rc != NMH_OK) return rc;
-  if (!mask) return PLAYER_FAIL(NMH_E_INVALID, "%s: mask is NULL", fn);
-  if (mask_kind != NMH_MASK_F32 && mask_kind != NMH_MASK_U8)
-    return PLAYER_FAIL(NMH_E_INVALID, "%s: unknown mask_kind %d", fn, mask_kind);
-  if (!out) return PLAYER_FAIL(NMH_E_INVALID, "%s: %s is NULL", fn, out_name);
-  for (int h = 0; h < ph->n_heads; ++h) {
-    if (ph->mask_off[h] < 0 || ph->out_off[h] < 0)
-      return PLAYER_FAIL(NMH_E_INVALID, "%s: mask_off[%d] %d or out_off[%d] %d is negative", fn, h, ph->mask_off[h],
-                         h, ph->out_off[h]);
-    if (mask_stride < (int64_t)ph->mask_off[h] + set_rows + 1)
-      return PLAYER_FAIL(NMH_E_INVALID, "%s: mask_stride %lld < mask_off[%d] + set_rows + 1 = %lld", fn,
-                         (long long)mask_stride, h, (long long)ph->mask_off[h] + set_rows + 1);
-    if (out_stride < (int64_t)ph->out_off[h] + set_rows + 1)
-      return PLAYER_FAIL(NMH_E_INVALID, "%s: %s %lld < out_off[%d] + set_rows + 1 = %lld", fn, stride_name,
-                         (long long)out_stride, h, (long long)ph->out_off[h] + set_rows + 1);
-  }
-  return NMH_OK;
-}
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace
 
 extern "C" {
@@ -337,16 +274,16 @@ int nmh_player_features(int32_t n_sets, const void* ents, int64_t ent_stride, in
                         const void* ids, int64_t id_stride, int32_t id_kind, float* features, float* sums,
                         float* mine, int32_t* mine_idx, void* stream) {
   const char* fn = "nmh_player_features";
-  if (n_sets < 0) return PLAYER_FAIL(NMH_E_INVALID, "%s: n_sets %d is negative", fn, n_sets);
-  const int rc = check_set(fn, ents, ent_stride, ent_kind, set_rows);
+  if (n_sets < 0) return heads_fail(NMH_E_INVALID, "%s: n_sets %d is negative", fn, n_sets);
+  const int rc = check_set(fn, kEntitySets, ents, ent_stride, ent_kind, set_rows);
   if (rc != NMH_OK) return rc;
   if (!features && !sums && !mine && !mine_idx)
-    return PLAYER_FAIL(NMH_E_INVALID, "%s: features, sums, mine and mine_idx are all NULL", fn);
+    return heads_fail(NMH_E_INVALID, "%s: features, sums, mine and mine_idx are all NULL", fn);
   if (mine || mine_idx) {
-    if (!ids) return PLAYER_FAIL(NMH_E_INVALID, "%s: ids is NULL but mine or mine_idx is not", fn);
+    if (!ids) return heads_fail(NMH_E_INVALID, "%s: ids is NULL but mine or mine_idx is not", fn);
     if (id_kind != NMH_PLAYER_F32 && id_kind != NMH_PLAYER_I16)
-      return PLAYER_FAIL(NMH_E_INVALID, "%s: unknown id_kind %d", fn, id_kind);
-    if (id_stride < 1) return PLAYER_FAIL(NMH_E_INVALID, "%s: id_stride %lld < 1", fn, (long long)id_stride);
+      return heads_fail(NMH_E_INVALID, "%s: unknown id_kind %d", fn, id_kind);
+    if (id_stride < 1) return heads_fail(NMH_E_INVALID, "%s: id_stride %lld < 1", fn, (long long)id_stride);
   }
   if (n_sets == 0) return NMH_OK;
   const bool f32 = ent_kind == NMH_PLAYER_F32;
@@ -360,7 +297,7 @@ int nmh_player_features(int32_t n_sets, const void* ents, int64_t ent_stride, in
       hipLaunchKernelGGL(nmh_player_own_kernel<int16_t>, grid, block, 0, st, n_sets,
                          static_cast<const int16_t*>(ents), ent_stride, set_rows, ids, id_stride, id_kind, mine,
                          mine_idx);
-    return launched(fn);
+    return heads_launched(fn);
   }
   const dim3 grid((unsigned)n_sets), block(kThreads);
   if (f32)
@@ -369,50 +306,36 @@ int nmh_player_features(int32_t n_sets, const void* ents, int64_t ent_stride, in
   else
     hipLaunchKernelGGL(nmh_player_features_kernel<int16_t>, grid, block, 0, st, static_cast<const int16_t*>(ents),
                        ent_stride, set_rows, ids, id_stride, id_kind, features, sums, mine, mine_idx);
-  return launched(fn);
+  return heads_launched(fn);
 }
-
-#define PLAYER_LAUNCH(K, ...)                                                                             \
-  do {                                                                                                    \
-    const dim3 grid((unsigned)((n_rows + kRowsPerBlock - 1) / kRowsPerBlock)), block(64 * kRowsPerBlock); \
-    hipStream_t st = static_cast<hipStream_t>(stream);                                                    \
-    const bool mf = mask_kind == NMH_MASK_F32;                                                            \
-    if (ent_kind == NMH_PLAYER_F32) {                                                                     \
-      auto* kern = mf ? K<float, NMH_MASK_F32> : K<float, NMH_MASK_U8>;                                   \
-      hipLaunchKernelGGL(kern, grid, block, 0, st, *ph, n_rows, static_cast<const float*>(ents), __VA_ARGS__);   \
-    } else {                                                                                              \
-      auto* kern = mf ? K<int16_t, NMH_MASK_F32> : K<int16_t, NMH_MASK_U8>;                               \
-      hipLaunchKernelGGL(kern, grid, block, 0, st, *ph, n_rows, static_cast<const int16_t*>(ents), __VA_ARGS__); \
-    }                                                                                                     \
-  } while (0)
 
 int nmh_player_logits(const NmhPlayerHeads* ph, int32_t n_rows, const void* ents, int64_t ent_stride,
                       int32_t ent_kind, int32_t set_rows, const void* mask, int64_t mask_stride, int32_t mask_kind,
                       const float* pq, float* out, int64_t out_stride, void* stream) {
   const char* fn = "nmh_player_logits";
-  const int rc = check_logits(fn, ph, n_rows, ents, ent_stride, ent_kind, set_rows, mask, mask_stride, mask_kind,
-                              "out", out, "out_stride", out_stride);
+  const int rc = check_logits(fn, kEntitySets, ph, n_rows, ents, ent_stride, ent_kind, set_rows, 1, mask, mask_stride,
+                              mask_kind, "out", out, "out_stride", out_stride);
   if (rc != NMH_OK) return rc;
-  if (!pq) return PLAYER_FAIL(NMH_E_INVALID, "%s: pq is NULL", fn);
-  if (!aligned16(pq)) return PLAYER_FAIL(NMH_E_INVALID, "%s: pq is not 16-byte aligned", fn);
+  if (!pq) return heads_fail(NMH_E_INVALID, "%s: pq is NULL", fn);
+  if (!aligned16(pq)) return heads_fail(NMH_E_INVALID, "%s: pq is not 16-byte aligned", fn);
   if (n_rows == 0) return NMH_OK;
-  PLAYER_LAUNCH(nmh_player_logits_kernel, ent_stride, set_rows, mask, mask_stride, pq, out, out_stride);
-  return launched(fn);
+  HEADS_SET_LAUNCH(nmh_player_logits_kernel, ent_kind, mask_kind, kRowsPerBlock, stream, ph, n_rows, ents, ent_stride,
+                   set_rows, mask, mask_stride, pq, out, out_stride);
+  return heads_launched(fn);
 }
 
 int nmh_player_logits_backward(const NmhPlayerHeads* ph, int32_t n_rows, const void* ents, int64_t ent_stride,
                                int32_t ent_kind, int32_t set_rows, const void* mask, int64_t mask_stride,
                                int32_t mask_kind, const float* g_out, int64_t g_stride, float* g_pq, void* stream) {
   const char* fn = "nmh_player_logits_backward";
-  const int rc = check_logits(fn, ph, n_rows, ents, ent_stride, ent_kind, set_rows, mask, mask_stride, mask_kind,
-                              "g_out", g_out, "g_stride", g_stride);
+  const int rc = check_logits(fn, kEntitySets, ph, n_rows, ents, ent_stride, ent_kind, set_rows, 1, mask, mask_stride,
+                              mask_kind, "g_out", g_out, "g_stride", g_stride);
   if (rc != NMH_OK) return rc;
-  if (!g_pq) return PLAYER_FAIL(NMH_E_INVALID, "%s: g_pq is NULL", fn);
+  if (!g_pq) return heads_fail(NMH_E_INVALID, "%s: g_pq is NULL", fn);
   if (n_rows == 0) return NMH_OK;
-  PLAYER_LAUNCH(nmh_player_logits_backward_kernel, ent_stride, set_rows, mask, mask_stride, g_out, g_stride, g_pq);
-  return launched(fn);
+  HEADS_SET_LAUNCH(nmh_player_logits_backward_kernel, ent_kind, mask_kind, kRowsPerBlock, stream, ph, n_rows, ents,
+                   ent_stride, set_rows, mask, mask_stride, g_out, g_stride, g_pq);
+  return heads_launched(fn);
 }
-
-#undef PLAYER_LAUNCH
 
 }  // extern "C"

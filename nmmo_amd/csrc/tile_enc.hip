@@ -40,11 +40,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "host_api.h"
+#include "heads_host.h"  // heads_fail, heads_launched, aligned16
 #include "../../include/nmmo_heads.h"
-
-// heads.hip: the message goes into the error text nmh_last_error() returns
-int heads_record_error(int code, const char* msg);
 
 namespace {
 
@@ -66,8 +63,6 @@ constexpr int kPadSide = kOut2Side + 4, kPad = kPadSide * kPadSide;  // dz2 insi
 static_assert(kRowOut % 4 == 0, "a row of out is whole float4s");
 static_assert(kT == kSide * kSide && kK == 9 && kO == 32 && kV == 256 && kF == 3, "the start-kit shape");
 static_assert(kO2 == 8 && kP2 == NMH_TILE2_OUT && kO2 * kO == kFwdThreads, "one thread per (o2, c) pair of g_W2");
-
-#define TILE_FAIL(code, ...) heads_record_error(fail(code, __VA_ARGS__), g_err.c_str())
 
 // SPEC §19's index rule. float32: (v - c) + 7 in two roundings, truncated, clamped, NaN -> 0.
 __device__ inline int tile_index(float v, float c, bool relative) {
@@ -396,30 +391,23 @@ __global__ __launch_bounds__(kBwdThreads) void nmh_tile_backward_kernel(
   }
 }
 
-int launched(const char* fn) {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? NMH_OK : TILE_FAIL(NMH_E_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
-}
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace
 
 extern "C" {
 
 int nmh_tile_forward(int32_t n_rows, const void* tile, int64_t tile_stride, int32_t tile_kind, const float* table,
                      const float* bias, float* out, uint8_t* idx_out, void* stream) {
-  if (n_rows < 0) return TILE_FAIL(NMH_E_INVALID, "nmh_tile_forward: n_rows %d is negative", n_rows);
-  if (!tile) return TILE_FAIL(NMH_E_INVALID, "nmh_tile_forward: tile is NULL");
-  if (!table) return TILE_FAIL(NMH_E_INVALID, "nmh_tile_forward: table is NULL");
-  if (!bias) return TILE_FAIL(NMH_E_INVALID, "nmh_tile_forward: bias is NULL");
-  if (!out) return TILE_FAIL(NMH_E_INVALID, "nmh_tile_forward: out is NULL");
+  if (n_rows < 0) return heads_fail(NMH_E_INVALID, "nmh_tile_forward: n_rows %d is negative", n_rows);
+  if (!tile) return heads_fail(NMH_E_INVALID, "nmh_tile_forward: tile is NULL");
+  if (!table) return heads_fail(NMH_E_INVALID, "nmh_tile_forward: table is NULL");
+  if (!bias) return heads_fail(NMH_E_INVALID, "nmh_tile_forward: bias is NULL");
+  if (!out) return heads_fail(NMH_E_INVALID, "nmh_tile_forward: out is NULL");
   if (tile_kind != NMH_TILE_F32 && tile_kind != NMH_TILE_I16)
-    return TILE_FAIL(NMH_E_INVALID, "nmh_tile_forward: unknown tile_kind %d", tile_kind);
+    return heads_fail(NMH_E_INVALID, "nmh_tile_forward: unknown tile_kind %d", tile_kind);
   if (tile_stride < kRowIdx)
-    return TILE_FAIL(NMH_E_INVALID, "nmh_tile_forward: tile_stride %lld < %d", (long long)tile_stride, kRowIdx);
+    return heads_fail(NMH_E_INVALID, "nmh_tile_forward: tile_stride %lld < %d", (long long)tile_stride, kRowIdx);
   if (!aligned16(table) || !aligned16(bias))
-    return TILE_FAIL(NMH_E_INVALID, "nmh_tile_forward: table or bias is not 16-byte aligned");
+    return heads_fail(NMH_E_INVALID, "nmh_tile_forward: table or bias is not 16-byte aligned");
   if (n_rows == 0) return NMH_OK;
   const dim3 grid((unsigned)((n_rows + kFwdRows - 1) / kFwdRows)), block(kFwdThreads);
   if (tile_kind == NMH_TILE_F32)
@@ -428,45 +416,45 @@ int nmh_tile_forward(int32_t n_rows, const void* tile, int64_t tile_stride, int3
   else
     hipLaunchKernelGGL(nmh_tile_forward_kernel<int16_t>, grid, block, 0, static_cast<hipStream_t>(stream), n_rows,
                        static_cast<const int16_t*>(tile), tile_stride, table, bias, out, idx_out);
-  return launched("nmh_tile_forward");
+  return heads_launched("nmh_tile_forward");
 }
 
 int nmh_tile_backward(int32_t n_rows, const uint8_t* idx, const float* out, const float* g_out, int32_t n_chunks,
                       float* g_table_parts, float* g_bias_parts, void* stream) {
-  if (n_rows < 0) return TILE_FAIL(NMH_E_INVALID, "nmh_tile_backward: n_rows %d is negative", n_rows);
-  if (!idx) return TILE_FAIL(NMH_E_INVALID, "nmh_tile_backward: idx is NULL");
-  if (!out) return TILE_FAIL(NMH_E_INVALID, "nmh_tile_backward: out is NULL");
-  if (!g_out) return TILE_FAIL(NMH_E_INVALID, "nmh_tile_backward: g_out is NULL");
+  if (n_rows < 0) return heads_fail(NMH_E_INVALID, "nmh_tile_backward: n_rows %d is negative", n_rows);
+  if (!idx) return heads_fail(NMH_E_INVALID, "nmh_tile_backward: idx is NULL");
+  if (!out) return heads_fail(NMH_E_INVALID, "nmh_tile_backward: out is NULL");
+  if (!g_out) return heads_fail(NMH_E_INVALID, "nmh_tile_backward: g_out is NULL");
   if (!g_table_parts || !g_bias_parts)
-    return TILE_FAIL(NMH_E_INVALID, "nmh_tile_backward: g_table_parts or g_bias_parts is NULL");
+    return heads_fail(NMH_E_INVALID, "nmh_tile_backward: g_table_parts or g_bias_parts is NULL");
   if (n_chunks < 1 || n_chunks > NMH_TILE_MAX_CHUNKS)
-    return TILE_FAIL(NMH_E_INVALID, "nmh_tile_backward: n_chunks %d outside 1..%d", n_chunks, NMH_TILE_MAX_CHUNKS);
+    return heads_fail(NMH_E_INVALID, "nmh_tile_backward: n_chunks %d outside 1..%d", n_chunks, NMH_TILE_MAX_CHUNKS);
   if (!aligned16(out) || !aligned16(g_out))
-    return TILE_FAIL(NMH_E_INVALID, "nmh_tile_backward: out or g_out is not 16-byte aligned");
+    return heads_fail(NMH_E_INVALID, "nmh_tile_backward: out or g_out is not 16-byte aligned");
   if (n_rows == 0) return NMH_OK;
   const int rows_per_chunk = (int)(((int64_t)n_rows + n_chunks - 1) / n_chunks);
   hipLaunchKernelGGL(nmh_tile_backward_kernel<false>, dim3((unsigned)(n_chunks * kSlices)), dim3(kBwdThreads), 0,
                      static_cast<hipStream_t>(stream), n_rows, rows_per_chunk, idx, out, g_out, g_table_parts,
                      g_bias_parts);
-  return launched("nmh_tile_backward");
+  return heads_launched("nmh_tile_backward");
 }
 
 int nmh_tile2_forward(int32_t n_rows, const void* tile, int64_t tile_stride, int32_t tile_kind, const float* table,
                       const float* bias1, const float* w2, const float* bias2, float* out2, uint8_t* idx_out,
                       void* stream) {
-  if (n_rows < 0) return TILE_FAIL(NMH_E_INVALID, "nmh_tile2_forward: n_rows %d is negative", n_rows);
-  if (!tile) return TILE_FAIL(NMH_E_INVALID, "nmh_tile2_forward: tile is NULL");
-  if (!table) return TILE_FAIL(NMH_E_INVALID, "nmh_tile2_forward: table is NULL");
-  if (!bias1) return TILE_FAIL(NMH_E_INVALID, "nmh_tile2_forward: bias1 is NULL");
-  if (!w2) return TILE_FAIL(NMH_E_INVALID, "nmh_tile2_forward: w2 is NULL");
-  if (!bias2) return TILE_FAIL(NMH_E_INVALID, "nmh_tile2_forward: bias2 is NULL");
-  if (!out2) return TILE_FAIL(NMH_E_INVALID, "nmh_tile2_forward: out2 is NULL");
+  if (n_rows < 0) return heads_fail(NMH_E_INVALID, "nmh_tile2_forward: n_rows %d is negative", n_rows);
+  if (!tile) return heads_fail(NMH_E_INVALID, "nmh_tile2_forward: tile is NULL");
+  if (!table) return heads_fail(NMH_E_INVALID, "nmh_tile2_forward: table is NULL");
+  if (!bias1) return heads_fail(NMH_E_INVALID, "nmh_tile2_forward: bias1 is NULL");
+  if (!w2) return heads_fail(NMH_E_INVALID, "nmh_tile2_forward: w2 is NULL");
+  if (!bias2) return heads_fail(NMH_E_INVALID, "nmh_tile2_forward: bias2 is NULL");
+  if (!out2) return heads_fail(NMH_E_INVALID, "nmh_tile2_forward: out2 is NULL");
   if (tile_kind != NMH_TILE_F32 && tile_kind != NMH_TILE_I16)
-    return TILE_FAIL(NMH_E_INVALID, "nmh_tile2_forward: unknown tile_kind %d", tile_kind);
+    return heads_fail(NMH_E_INVALID, "nmh_tile2_forward: unknown tile_kind %d", tile_kind);
   if (tile_stride < kRowIdx)
-    return TILE_FAIL(NMH_E_INVALID, "nmh_tile2_forward: tile_stride %lld < %d", (long long)tile_stride, kRowIdx);
+    return heads_fail(NMH_E_INVALID, "nmh_tile2_forward: tile_stride %lld < %d", (long long)tile_stride, kRowIdx);
   if (!aligned16(table) || !aligned16(bias1) || !aligned16(w2) || !aligned16(bias2))
-    return TILE_FAIL(NMH_E_INVALID, "nmh_tile2_forward: table, bias1, w2 or bias2 is not 16-byte aligned");
+    return heads_fail(NMH_E_INVALID, "nmh_tile2_forward: table, bias1, w2 or bias2 is not 16-byte aligned");
   if (n_rows == 0) return NMH_OK;
   const dim3 grid((unsigned)((n_rows + kFwd2Rows - 1) / kFwd2Rows)), block(kFwdThreads);
   if (tile_kind == NMH_TILE_F32)
@@ -475,45 +463,47 @@ int nmh_tile2_forward(int32_t n_rows, const void* tile, int64_t tile_stride, int
   else
     hipLaunchKernelGGL(nmh_tile2_forward_kernel<int16_t>, grid, block, 0, static_cast<hipStream_t>(stream), n_rows,
                        static_cast<const int16_t*>(tile), tile_stride, table, bias1, w2, bias2, out2, idx_out);
-  return launched("nmh_tile2_forward");
+  return heads_launched("nmh_tile2_forward");
 }
 
 int nmh_tile2_backward(int32_t n_rows, const uint8_t* idx, const float* out2, const float* g_out2, const float* table,
                        const float* bias1, const float* w2, int32_t n_table_chunks, int32_t n_w2_parts,
                        float* dz1_scratch, float* g_table_parts, float* g_bias1_parts, float* g_w2_parts,
                        float* g_bias2_parts, void* stream) {
-  if (n_rows < 0) return TILE_FAIL(NMH_E_INVALID, "nmh_tile2_backward: n_rows %d is negative", n_rows);
-  if (!idx) return TILE_FAIL(NMH_E_INVALID, "nmh_tile2_backward: idx is NULL");
-  if (!out2) return TILE_FAIL(NMH_E_INVALID, "nmh_tile2_backward: out2 is NULL");
-  if (!g_out2) return TILE_FAIL(NMH_E_INVALID, "nmh_tile2_backward: g_out2 is NULL");
-  if (!table) return TILE_FAIL(NMH_E_INVALID, "nmh_tile2_backward: table is NULL");
-  if (!bias1) return TILE_FAIL(NMH_E_INVALID, "nmh_tile2_backward: bias1 is NULL");
-  if (!w2) return TILE_FAIL(NMH_E_INVALID, "nmh_tile2_backward: w2 is NULL");
-  if (!dz1_scratch) return TILE_FAIL(NMH_E_INVALID, "nmh_tile2_backward: dz1_scratch is NULL");
+  if (n_rows < 0) return heads_fail(NMH_E_INVALID, "nmh_tile2_backward: n_rows %d is negative", n_rows);
+  if (!idx) return heads_fail(NMH_E_INVALID, "nmh_tile2_backward: idx is NULL");
+  if (!out2) return heads_fail(NMH_E_INVALID, "nmh_tile2_backward: out2 is NULL");
+  if (!g_out2) return heads_fail(NMH_E_INVALID, "nmh_tile2_backward: g_out2 is NULL");
+  if (!table) return heads_fail(NMH_E_INVALID, "nmh_tile2_backward: table is NULL");
+  if (!bias1) return heads_fail(NMH_E_INVALID, "nmh_tile2_backward: bias1 is NULL");
+  if (!w2) return heads_fail(NMH_E_INVALID, "nmh_tile2_backward: w2 is NULL");
+  if (!dz1_scratch) return heads_fail(NMH_E_INVALID, "nmh_tile2_backward: dz1_scratch is NULL");
   if (!g_table_parts || !g_bias1_parts)
-    return TILE_FAIL(NMH_E_INVALID, "nmh_tile2_backward: g_table_parts or g_bias1_parts is NULL");
+    return heads_fail(NMH_E_INVALID, "nmh_tile2_backward: g_table_parts or g_bias1_parts is NULL");
   if (!g_w2_parts || !g_bias2_parts)
-    return TILE_FAIL(NMH_E_INVALID, "nmh_tile2_backward: g_w2_parts or g_bias2_parts is NULL");
+    return heads_fail(NMH_E_INVALID, "nmh_tile2_backward: g_w2_parts or g_bias2_parts is NULL");
   if (n_table_chunks < 1 || n_table_chunks > NMH_TILE_MAX_CHUNKS)
-    return TILE_FAIL(NMH_E_INVALID, "nmh_tile2_backward: n_table_chunks %d outside 1..%d", n_table_chunks,
-                     NMH_TILE_MAX_CHUNKS);
+    return heads_fail(NMH_E_INVALID, "nmh_tile2_backward: n_table_chunks %d outside 1..%d", n_table_chunks,
+                      NMH_TILE_MAX_CHUNKS);
   if (n_w2_parts < 1 || n_w2_parts > NMH_TILE2_MAX_PARTS)
-    return TILE_FAIL(NMH_E_INVALID, "nmh_tile2_backward: n_w2_parts %d outside 1..%d", n_w2_parts, NMH_TILE2_MAX_PARTS);
+    return heads_fail(NMH_E_INVALID, "nmh_tile2_backward: n_w2_parts %d outside 1..%d", n_w2_parts,
+                      NMH_TILE2_MAX_PARTS);
   if (!aligned16(table) || !aligned16(bias1) || !aligned16(w2))
-    return TILE_FAIL(NMH_E_INVALID, "nmh_tile2_backward: table, bias1 or w2 is not 16-byte aligned");
-  if (!aligned16(dz1_scratch)) return TILE_FAIL(NMH_E_INVALID, "nmh_tile2_backward: dz1_scratch is not 16-byte aligned");
+    return heads_fail(NMH_E_INVALID, "nmh_tile2_backward: table, bias1 or w2 is not 16-byte aligned");
+  if (!aligned16(dz1_scratch))
+    return heads_fail(NMH_E_INVALID, "nmh_tile2_backward: dz1_scratch is not 16-byte aligned");
   if (n_rows == 0) return NMH_OK;
   const int rows_per_part = (int)(((int64_t)n_rows + n_w2_parts - 1) / n_w2_parts);
   hipLaunchKernelGGL(nmh_tile2_backward_kernel, dim3((unsigned)n_w2_parts), dim3(kFwdThreads), 0,
                      static_cast<hipStream_t>(stream), n_rows, rows_per_part, idx, out2, g_out2, table, bias1, w2,
                      dz1_scratch, g_w2_parts, g_bias2_parts);
-  const int rc = launched("nmh_tile2_backward");
+  const int rc = heads_launched("nmh_tile2_backward");
   if (rc != NMH_OK) return rc;
   const int rows_per_chunk = (int)(((int64_t)n_rows + n_table_chunks - 1) / n_table_chunks);
   hipLaunchKernelGGL(nmh_tile_backward_kernel<true>, dim3((unsigned)(n_table_chunks * kSlices)), dim3(kBwdThreads), 0,
                      static_cast<hipStream_t>(stream), n_rows, rows_per_chunk, idx, static_cast<const float*>(nullptr),
                      static_cast<const float*>(dz1_scratch), g_table_parts, g_bias1_parts);
-  return launched("nmh_tile2_backward");
+  return heads_launched("nmh_tile2_backward");
 }
 
 }  // extern "C"

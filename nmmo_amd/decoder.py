@@ -108,32 +108,18 @@ def _make_function():
                 if dense is None or dense.dtype != torch.float32 or tuple(dense.shape) != (n, n_dense):
                     raise ValueError(f"dense must be float32 [{n}, {n_dense}], got "
                                      f"{None if dense is None else (dense.dtype, tuple(dense.shape))}")
-                dense = dense.detach()
-                if dense.stride(1) != 1 or (n > 1 and dense.stride(0) < n_dense):
-                    dense = dense.contiguous()
-                d_stride = max(dense.stride(0), n_dense)
+                dense, d_stride = heads.rows_arg(dense.detach(), n_dense)
             else:
                 dense = None
             st = sets_struct(head_set, rules, rows, shares, strides, [x.data_ptr() for x in kept],
                              kinds[0] if kinds else ELEM_F32)
             mask, mptr, mstride, mkind = heads._mask_arg(mask, n, total)
-            a_in = None
-            if action is not None:
-                if tuple(action.shape) != (n, hd.n_heads):
-                    raise ValueError(f"action must be [{n}, {hd.n_heads}], got {tuple(action.shape)}")
-                a_in = action.to(device=dev, dtype=torch.int32).contiguous()
-            a_out = torch.empty((n, hd.n_heads), dtype=torch.int32, device=dev)
-            logprob = torch.empty(n, dtype=torch.float32, device=dev)
-            entropy = torch.empty(n, dtype=torch.float32, device=dev)
-            lse = torch.empty((n, hd.n_heads), dtype=torch.float32, device=dev)
-            hent = torch.empty((n, hd.n_heads), dtype=torch.float32, device=dev)
+            a_in, (a_out, logprob, entropy, lse, hent), io = heads.head_io(action, n, hd.n_heads, dev, seed, offset,
+                                                                          row_base)
             with torch.cuda.device(dev):
                 heads.check(heads.lib().nmh_decoder_forward(
-                    ctypes.byref(hd), ctypes.byref(st), n, None if pq is None else pq.data_ptr(),
-                    None if dense is None else dense.data_ptr(), d_stride, mptr, mstride, mkind,
-                    None if a_in is None else a_in.data_ptr(), int(seed) & (2**64 - 1), int(offset) & (2**64 - 1),
-                    int(row_base) & 0xFFFFFFFF, a_out.data_ptr(), logprob.data_ptr(), entropy.data_ptr(),
-                    lse.data_ptr(), hent.data_ptr(), heads._stream()), "nmh_decoder_forward")
+                    ctypes.byref(hd), ctypes.byref(st), n, heads.ptr(pq), heads.ptr(dense), d_stride, mptr, mstride,
+                    mkind, *io, heads._stream()), "nmh_decoder_forward")
             ctx.args = (hd, st, mstride, mkind, d_stride, n_dense, n_ptr)
             ctx.has = (dense is not None, pq is not None)
             ctx.set_materialize_grads(False)  # an unused logprob / entropy arrives as None -> NULL
@@ -153,7 +139,7 @@ def _make_function():
             g_q = torch.empty((n, n_ptr, QUERY), dtype=torch.float32, device=dev) if pq is not None and need[1] else None
             glp = None if g_logprob is None else g_logprob.to(torch.float32).contiguous()
             gen = None if g_entropy is None else g_entropy.to(torch.float32).contiguous()
-            ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+            ptr = heads.ptr
             with torch.cuda.device(dev):
                 heads.check(heads.lib().nmh_decoder_backward(
                     ctypes.byref(hd), ctypes.byref(st), n, ptr(pq), ptr(dense), d_stride, mask.data_ptr(), mstride,

@@ -94,6 +94,16 @@ def heads_struct(dims) -> NmhHeads:
     return hd
 
 
+def rows_arg(t, width: int):
+    """(tensor kept alive, row stride in elements) of t [n, >= width] whose rows' first `width` columns
+    the library reads in place: copied only if its columns are not consecutive or its rows overlap."""
+    s0, s1 = t.stride()
+    if s1 != 1 or (s0 < width and t.shape[0] > 1):
+        t = t[:, :width].contiguous()
+        s0 = t.stride(0)
+    return t, (s0 if s0 > width else width)
+
+
 def _mask_arg(mask, n_rows: int, total: int):
     """(tensor kept alive, data_ptr, row stride in elements, NMH_MASK_*) of a mask read in place."""
     import torch
@@ -106,15 +116,40 @@ def _mask_arg(mask, n_rows: int, total: int):
         kind = MASK_U8
     else:
         raise TypeError(f"mask must be float32, uint8 or bool, got {mask.dtype}")
-    if mask.stride(1) != 1 or (n_rows > 1 and mask.stride(0) < total):
-        mask = mask[:, :total].contiguous()
-    return mask, mask.data_ptr(), max(mask.stride(0), total), kind
+    mask, stride = rows_arg(mask, total)
+    return mask, mask.data_ptr(), stride, kind
 
 
 def _stream():
     import torch
 
     return torch.cuda.current_stream().cuda_stream
+
+
+def ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def head_io(action, n: int, n_heads: int, dev, seed, offset, row_base):
+    """What every forward of the masked heads passes after its logits and mask: the actions to
+    evaluate (None: sample), the philox counter, and the five outputs, which it allocates. Returns
+    (a_in kept alive, (a_out, logprob, entropy, lse, hent), the arguments actions_in .. head_entropy)."""
+    import torch
+
+    a_in = None
+    if action is not None:
+        if tuple(action.shape) != (n, n_heads):
+            raise ValueError(f"action must be [{n}, {n_heads}], got {tuple(action.shape)}")
+        a_in = action.to(device=dev, dtype=torch.int32).contiguous()
+    a_out = torch.empty((n, n_heads), dtype=torch.int32, device=dev)
+    logprob = torch.empty(n, dtype=torch.float32, device=dev)
+    entropy = torch.empty(n, dtype=torch.float32, device=dev)
+    lse = torch.empty((n, n_heads), dtype=torch.float32, device=dev)
+    hent = torch.empty((n, n_heads), dtype=torch.float32, device=dev)
+    return a_in, (a_out, logprob, entropy, lse, hent), (
+        None if a_in is None else a_in.data_ptr(), int(seed) & (2**64 - 1), int(offset) & (2**64 - 1),
+        int(row_base) & 0xFFFFFFFF, a_out.data_ptr(), logprob.data_ptr(), entropy.data_ptr(), lse.data_ptr(),
+        hent.data_ptr())
 
 
 def _make_function():
@@ -130,27 +165,13 @@ def _make_function():
             if logits.dtype != torch.float32 or logits.dim() != 2 or logits.shape[1] != total:
                 raise ValueError(f"logits must be float32 [N, {total}], got {logits.dtype} {tuple(logits.shape)}")
             n = logits.shape[0]
-            logits = logits.detach()
-            if logits.stride(1) != 1 or (n > 1 and logits.stride(0) < total):
-                logits = logits.contiguous()
+            logits, lstride = rows_arg(logits.detach(), total)
             mask, mptr, mstride, kind = _mask_arg(mask, n, total)
             dev = logits.device
-            a_in = None
-            if action is not None:
-                if tuple(action.shape) != (n, hd.n_heads):
-                    raise ValueError(f"action must be [{n}, {hd.n_heads}], got {tuple(action.shape)}")
-                a_in = action.to(device=dev, dtype=torch.int32).contiguous()
-            a_out = torch.empty((n, hd.n_heads), dtype=torch.int32, device=dev)
-            logprob = torch.empty(n, dtype=torch.float32, device=dev)
-            entropy = torch.empty(n, dtype=torch.float32, device=dev)
-            lse = torch.empty((n, hd.n_heads), dtype=torch.float32, device=dev)
-            hent = torch.empty((n, hd.n_heads), dtype=torch.float32, device=dev)
+            a_in, (a_out, logprob, entropy, lse, hent), io = head_io(action, n, hd.n_heads, dev, seed, offset, row_base)
             with torch.cuda.device(dev):
-                check(lib().nmh_forward(
-                    ctypes.byref(hd), n, logits.data_ptr(), max(logits.stride(0), total), mptr, mstride, kind,
-                    None if a_in is None else a_in.data_ptr(), int(seed) & (2**64 - 1), int(offset) & (2**64 - 1),
-                    int(row_base) & 0xFFFFFFFF, a_out.data_ptr(), logprob.data_ptr(), entropy.data_ptr(),
-                    lse.data_ptr(), hent.data_ptr(), _stream()), "nmh_forward")
+                check(lib().nmh_forward(ctypes.byref(hd), n, logits.data_ptr(), lstride, mptr, mstride, kind, *io,
+                                        _stream()), "nmh_forward")
             ctx.hd, ctx.kind = hd, kind
             ctx.set_materialize_grads(False)  # an unused logprob / entropy arrives as None -> NULL
             ctx.save_for_backward(logits, mask, a_out, lse, hent)
@@ -169,8 +190,7 @@ def _make_function():
                 check(lib().nmh_backward(
                     ctypes.byref(hd), n, logits.data_ptr(), max(logits.stride(0), total), mask.data_ptr(),
                     max(mask.stride(0), total), ctx.kind, actions.data_ptr(), lse.data_ptr(), hent.data_ptr(),
-                    None if glp is None else glp.data_ptr(), None if gen is None else gen.data_ptr(),
-                    g_logits.data_ptr(), total, _stream()), "nmh_backward")
+                    ptr(glp), ptr(gen), g_logits.data_ptr(), total, _stream()), "nmh_backward")
             return g_logits, None, None, None, None, None, None
 
     return MaskedHeads
@@ -238,7 +258,7 @@ def _dense16(t):
 
 
 def _key_array(tensors):
-    return (ctypes.c_void_p * max(1, len(tensors)))(*[None if t is None else t.data_ptr() for t in tensors])
+    return (ctypes.c_void_p * max(1, len(tensors)))(*[ptr(t) for t in tensors])
 
 
 def _make_pointer_function():
@@ -281,23 +301,11 @@ def _make_pointer_function():
             keys = [_dense16(kt) for kt in keys]
             pt = pointer_struct(dims, head_set, [kt.shape[1] for kt in keys], key_dim)
             mask, mptr, mstride, kind = _mask_arg(mask, n, total)
-            a_in = None
-            if action is not None:
-                if tuple(action.shape) != (n, hd.n_heads):
-                    raise ValueError(f"action must be [{n}, {hd.n_heads}], got {tuple(action.shape)}")
-                a_in = action.to(device=dev, dtype=torch.int32).contiguous()
-            a_out = torch.empty((n, hd.n_heads), dtype=torch.int32, device=dev)
-            logprob = torch.empty(n, dtype=torch.float32, device=dev)
-            entropy = torch.empty(n, dtype=torch.float32, device=dev)
-            lse = torch.empty((n, hd.n_heads), dtype=torch.float32, device=dev)
-            hent = torch.empty((n, hd.n_heads), dtype=torch.float32, device=dev)
+            a_in, (a_out, logprob, entropy, lse, hent), io = head_io(action, n, hd.n_heads, dev, seed, offset, row_base)
             with torch.cuda.device(dev):
                 check(lib().nmh_pointer_forward(
-                    ctypes.byref(hd), ctypes.byref(pt), n, None if queries is None else queries.data_ptr(),
-                    _key_array(keys), None if dense is None else dense.data_ptr(), n_dense, mptr, mstride, kind,
-                    None if a_in is None else a_in.data_ptr(), int(seed) & (2**64 - 1), int(offset) & (2**64 - 1),
-                    int(row_base) & 0xFFFFFFFF, a_out.data_ptr(), logprob.data_ptr(), entropy.data_ptr(),
-                    lse.data_ptr(), hent.data_ptr(), _stream()), "nmh_pointer_forward")
+                    ctypes.byref(hd), ctypes.byref(pt), n, ptr(queries), _key_array(keys), ptr(dense), n_dense, mptr,
+                    mstride, kind, *io, _stream()), "nmh_pointer_forward")
             ctx.hd, ctx.pt, ctx.kind, ctx.n_dense = hd, pt, kind, n_dense
             ctx.has = (queries is not None, dense is not None)
             ctx.set_materialize_grads(False)
@@ -321,12 +329,10 @@ def _make_pointer_function():
             gen = None if g_entropy is None else g_entropy.to(torch.float32).contiguous()
             with torch.cuda.device(dev):
                 check(lib().nmh_pointer_backward(
-                    ctypes.byref(hd), ctypes.byref(pt), n, None if queries is None else queries.data_ptr(),
-                    _key_array(keys), None if dense is None else dense.data_ptr(), ctx.n_dense, mask.data_ptr(),
-                    max(mask.stride(0), total), ctx.kind, actions.data_ptr(), lse.data_ptr(), hent.data_ptr(),
-                    None if glp is None else glp.data_ptr(), None if gen is None else gen.data_ptr(),
-                    None if g_d is None else g_d.data_ptr(), ctx.n_dense, None if g_q is None else g_q.data_ptr(),
-                    _key_array(g_k), _stream()), "nmh_pointer_backward")
+                    ctypes.byref(hd), ctypes.byref(pt), n, ptr(queries), _key_array(keys), ptr(dense), ctx.n_dense,
+                    mask.data_ptr(), max(mask.stride(0), total), ctx.kind, actions.data_ptr(), lse.data_ptr(),
+                    hent.data_ptr(), ptr(glp), ptr(gen), ptr(g_d), ctx.n_dense, ptr(g_q), _key_array(g_k), _stream()),
+                    "nmh_pointer_backward")
             return (g_q, g_d, None, None, None, None, None, None, None, *g_k)
 
     return PointerHeads

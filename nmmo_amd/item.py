@@ -22,13 +22,11 @@ There is no torch fallback for the fused path: a host tensor, or a missing libra
 
 from __future__ import annotations
 
-import ctypes
-
 import torch
 from torch import nn
 from torch.nn import functional as F
 
-from . import heads
+from . import _sets, heads
 from .heads import HeadsError
 
 COLS, FEATURES, TYPES, QUERY = 16, 32, 18, 36
@@ -39,20 +37,12 @@ CONT_COLS = [3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 15]
 SCALE = 0.01  # applied as the float32 nearest 0.01, the reference's `continuous_scale`
 
 
-class NmhItemHeads(ctypes.Structure):
-    _fields_ = [("n_heads", ctypes.c_int32), ("mask_off", ctypes.c_int32 * MAX_HEADS),
-                ("out_off", ctypes.c_int32 * MAX_HEADS)]
+SPEC = _sets.SetSpec("item_logits", "nmh_item_logits", "items", "M", "items", "item", COLS, QUERY, MAX_ROWS, share=True)
+NmhItemHeads = _sets.NmhSetHeads
 
 
 def item_heads_struct(mask_off, out_off) -> NmhItemHeads:
-    mask_off, out_off = [int(o) for o in mask_off], [int(o) for o in out_off]
-    if not 1 <= len(mask_off) <= MAX_HEADS or len(out_off) != len(mask_off):
-        raise ValueError(f"between 1 and {MAX_HEADS} heads over one item set, got {len(mask_off)}")
-    ih = NmhItemHeads()
-    ih.n_heads = len(mask_off)
-    for h, (m, o) in enumerate(zip(mask_off, out_off)):
-        ih.mask_off[h], ih.out_off[h] = m, o
-    return ih
+    return _sets.set_heads_struct(mask_off, out_off, "item")
 
 
 def item_features_ref(items: torch.Tensor) -> torch.Tensor:
@@ -70,30 +60,7 @@ def item_features_ref(items: torch.Tensor) -> torch.Tensor:
 
 def _item_arg(x: torch.Tensor, set_rows):
     """(tensor kept alive, set stride in elements, R, NMH_ITEM_*) of item sets read in place."""
-    if x.dim() == 3:
-        if x.shape[2] != COLS:
-            raise ValueError(f"items must be [M, R, {COLS}] or [M, >= {COLS} R], got {tuple(x.shape)}")
-        rows = x.shape[1]
-        if x.stride(2) != 1 or x.stride(1) != COLS:
-            x = x.contiguous()
-        x = x.as_strided((x.shape[0], rows * COLS), (x.stride(0), 1), x.storage_offset())  # the same memory
-    elif x.dim() == 2:
-        rows = x.shape[1] // COLS if set_rows is None else int(set_rows)
-    else:
-        raise ValueError(f"items must be [M, R, {COLS}] or [M, >= {COLS} R], got {tuple(x.shape)}")
-    if set_rows is not None and int(set_rows) != rows:
-        raise ValueError(f"set_rows {set_rows} does not match items {tuple(x.shape)}")
-    if not 1 <= rows <= MAX_ROWS or x.shape[1] < rows * COLS:
-        raise ValueError(f"a set has 1..{MAX_ROWS} items of {COLS} columns, got {rows} in {tuple(x.shape)}")
-    if x.dtype == torch.float32:
-        kind = ITEM_F32
-    elif x.dtype == torch.int16:
-        kind = ITEM_I16
-    else:
-        raise TypeError(f"items must be float32 or int16, got {x.dtype}")
-    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < rows * COLS):
-        x = x[:, :rows * COLS].contiguous()
-    return x, max(x.stride(0), rows * COLS), rows, kind
+    return _sets.set_arg(x, set_rows, SPEC)
 
 
 def _features(items, set_rows, want_features: bool, want_sums: bool):
@@ -126,48 +93,6 @@ def item_sums(items: torch.Tensor, *, set_rows=None) -> torch.Tensor:
     return _features(items, set_rows, False, True)[1]
 
 
-class _ItemLogits(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, items, pq, mask_rows, mask_off, share, mask_kind, set_rows):
-        if not (items.is_cuda and pq.is_cuda and mask_rows.is_cuda):
-            raise HeadsError("item_logits runs on the GPU: items, pq and mask_rows must be device tensors")
-        x, stride, rows, kind = _item_arg(items.detach(), set_rows)
-        n_heads = len(mask_off)
-        n, dev = mask_rows.shape[0], x.device
-        if pq.dtype != torch.float32 or tuple(pq.shape) != (n, n_heads, QUERY):
-            raise ValueError(f"pq must be float32 [{n}, {n_heads}, {QUERY}], got {pq.dtype} {tuple(pq.shape)}")
-        share = int(share)
-        if share < 1 or x.shape[0] * share < n:
-            raise ValueError(f"{x.shape[0]} item sets shared by {share} rows each do not cover {n} rows")
-        width = rows + 1
-        ih = item_heads_struct(mask_off, [h * width for h in range(n_heads)])
-        mask, mptr, mstride, mkind = heads._mask_arg(mask_rows, n, max(int(o) for o in mask_off) + width)
-        if mask_kind is not None and mask_kind != mkind:
-            raise ValueError(f"mask_kind {mask_kind} does not match the mask's dtype {mask_rows.dtype}")
-        pq = heads._dense16(pq)
-        out = torch.empty((n, n_heads * width), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            heads.check(heads.lib().nmh_item_logits(
-                ctypes.byref(ih), n, x.data_ptr(), stride, kind, rows, share, mptr, mstride, mkind, pq.data_ptr(),
-                out.data_ptr(), n_heads * width, heads._stream()), "nmh_item_logits")
-        ctx.args = (ih, stride, kind, rows, share, mstride, mkind, n_heads)
-        ctx.save_for_backward(x, mask)
-        return out
-
-    @staticmethod
-    def backward(ctx, g_out):
-        x, mask = ctx.saved_tensors
-        ih, stride, kind, rows, share, mstride, mkind, n_heads = ctx.args
-        n, dev = mask.shape[0], x.device
-        g_out = g_out.to(torch.float32).contiguous()
-        g_pq = torch.empty((n, n_heads, QUERY), dtype=torch.float32, device=dev)  # (n == 0: empty, nothing to write)
-        with torch.cuda.device(dev):
-            heads.check(heads.lib().nmh_item_logits_backward(
-                ctypes.byref(ih), n, x.data_ptr(), stride, kind, rows, share, mask.data_ptr(), mstride, mkind,
-                g_out.data_ptr(), n_heads * (rows + 1), g_pq.data_ptr(), heads._stream()), "nmh_item_logits_backward")
-        return None, g_pq, None, None, None, None, None
-
-
 def item_logits(items: torch.Tensor, pq: torch.Tensor, mask_rows: torch.Tensor, mask_off, *, share: int = 1,
                 mask_kind=None, set_rows=None) -> torch.Tensor:
     """The logits [N, len(mask_off) * (R + 1)] of up to four pointer heads over one item set per
@@ -182,7 +107,7 @@ def item_logits(items: torch.Tensor, pq: torch.Tensor, mask_rows: torch.Tensor, 
     reference's zero padding row) are 0.0, and illegal candidates' items are never read. The
     backward gives pq's gradient alone, without atomics: the same bits on every run. The items
     and the mask must not be rewritten between forward and backward."""
-    return _ItemLogits.apply(items, pq, mask_rows, tuple(int(o) for o in mask_off), share, mask_kind, set_rows)
+    return _sets.SetLogits.apply(SPEC, items, pq, mask_rows, tuple(int(o) for o in mask_off), share, mask_kind, set_rows)
 
 
 class ItemEncoder(nn.Module):

@@ -24,13 +24,11 @@ There is no torch fallback for the fused path: a host tensor, or a missing libra
 
 from __future__ import annotations
 
-import ctypes
-
 import torch
 from torch import nn
 from torch.nn import functional as F
 
-from . import heads
+from . import _sets, heads
 from .heads import HeadsError
 
 COLS, FEATURES, TYPES, QUERY = 31, 35, 5, 40
@@ -39,20 +37,14 @@ PLAYER_F32, PLAYER_I16 = 0, 1
 ID_COL, TYPE_COL = 0, 1
 
 
-class NmhPlayerHeads(ctypes.Structure):
-    _fields_ = [("n_heads", ctypes.c_int32), ("mask_off", ctypes.c_int32 * MAX_HEADS),
-                ("out_off", ctypes.c_int32 * MAX_HEADS)]
+SPEC = _sets.SetSpec("player_logits", "nmh_player_logits", "ents", "N", "entities", "entity", COLS, QUERY, MAX_ROWS,
+                     share=False)
+NmhPlayerHeads = _sets.NmhSetHeads
+_kind, _ptr = _sets.elem_kind, heads.ptr
 
 
 def player_heads_struct(mask_off, out_off) -> NmhPlayerHeads:
-    mask_off, out_off = [int(o) for o in mask_off], [int(o) for o in out_off]
-    if not 1 <= len(mask_off) <= MAX_HEADS or len(out_off) != len(mask_off):
-        raise ValueError(f"between 1 and {MAX_HEADS} heads over one entity set, got {len(mask_off)}")
-    ph = NmhPlayerHeads()
-    ph.n_heads = len(mask_off)
-    for h, (m, o) in enumerate(zip(mask_off, out_off)):
-        ph.mask_off[h], ph.out_off[h] = m, o
-    return ph
+    return _sets.set_heads_struct(mask_off, out_off, "entity")
 
 
 def player_features_ref(ents: torch.Tensor) -> torch.Tensor:
@@ -76,35 +68,9 @@ def own_row_ref(ents: torch.Tensor, ids: torch.Tensor):
     return feats[torch.arange(feats.shape[0], device=feats.device), idx], idx
 
 
-def _kind(t: torch.Tensor, what: str) -> int:
-    if t.dtype == torch.float32:
-        return PLAYER_F32
-    if t.dtype == torch.int16:
-        return PLAYER_I16
-    raise TypeError(f"{what} must be float32 or int16, got {t.dtype}")
-
-
 def _ent_arg(x: torch.Tensor, set_rows):
     """(tensor kept alive, set stride in elements, R, NMH_PLAYER_*) of entity sets read in place."""
-    if x.dim() == 3:
-        if x.shape[2] != COLS:
-            raise ValueError(f"ents must be [N, R, {COLS}] or [N, >= {COLS} R], got {tuple(x.shape)}")
-        rows = x.shape[1]
-        if x.stride(2) != 1 or x.stride(1) != COLS:
-            x = x.contiguous()
-        x = x.as_strided((x.shape[0], rows * COLS), (x.stride(0), 1), x.storage_offset())  # the same memory
-    elif x.dim() == 2:
-        rows = x.shape[1] // COLS if set_rows is None else int(set_rows)
-    else:
-        raise ValueError(f"ents must be [N, R, {COLS}] or [N, >= {COLS} R], got {tuple(x.shape)}")
-    if set_rows is not None and int(set_rows) != rows:
-        raise ValueError(f"set_rows {set_rows} does not match ents {tuple(x.shape)}")
-    if not 1 <= rows <= MAX_ROWS or x.shape[1] < rows * COLS:
-        raise ValueError(f"a set has 1..{MAX_ROWS} entities of {COLS} columns, got {rows} in {tuple(x.shape)}")
-    kind = _kind(x, "ents")
-    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < rows * COLS):
-        x = x[:, :rows * COLS].contiguous()
-    return x, max(x.stride(0), rows * COLS), rows, kind
+    return _sets.set_arg(x, set_rows, SPEC)
 
 
 def _id_arg(ids: torch.Tensor, n: int):
@@ -118,10 +84,6 @@ def _id_arg(ids: torch.Tensor, n: int):
     if n > 1 and ids.stride(0) < 1:
         ids = ids.contiguous()
     return ids, max(ids.stride(0), 1), kind
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 def _features(ents, ids, set_rows, want: str):
@@ -168,48 +130,6 @@ def player_own(ents: torch.Tensor, ids: torch.Tensor, *, set_rows=None):
     return _features(ents, ids, set_rows, "own")[2:]
 
 
-class _PlayerLogits(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, ents, pq, mask_rows, mask_off, mask_kind, set_rows):
-        if not (ents.is_cuda and pq.is_cuda and mask_rows.is_cuda):
-            raise HeadsError("player_logits runs on the GPU: ents, pq and mask_rows must be device tensors")
-        x, stride, rows, kind = _ent_arg(ents.detach(), set_rows)
-        n_heads = len(mask_off)
-        n, dev = mask_rows.shape[0], x.device
-        if pq.dtype != torch.float32 or tuple(pq.shape) != (n, n_heads, QUERY):
-            raise ValueError(f"pq must be float32 [{n}, {n_heads}, {QUERY}], got {pq.dtype} {tuple(pq.shape)}")
-        if x.shape[0] != n:
-            raise ValueError(f"{x.shape[0]} entity sets for {n} rows")
-        width = rows + 1
-        ph = player_heads_struct(mask_off, [h * width for h in range(n_heads)])
-        mask, mptr, mstride, mkind = heads._mask_arg(mask_rows, n, max(int(o) for o in mask_off) + width)
-        if mask_kind is not None and mask_kind != mkind:
-            raise ValueError(f"mask_kind {mask_kind} does not match the mask's dtype {mask_rows.dtype}")
-        pq = heads._dense16(pq)
-        out = torch.empty((n, n_heads * width), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            heads.check(heads.lib().nmh_player_logits(
-                ctypes.byref(ph), n, x.data_ptr(), stride, kind, rows, mptr, mstride, mkind, pq.data_ptr(),
-                out.data_ptr(), n_heads * width, heads._stream()), "nmh_player_logits")
-        ctx.args = (ph, stride, kind, rows, mstride, mkind, n_heads)
-        ctx.save_for_backward(x, mask)
-        return out
-
-    @staticmethod
-    def backward(ctx, g_out):
-        x, mask = ctx.saved_tensors
-        ph, stride, kind, rows, mstride, mkind, n_heads = ctx.args
-        n, dev = mask.shape[0], x.device
-        g_out = g_out.to(torch.float32).contiguous()
-        g_pq = torch.empty((n, n_heads, QUERY), dtype=torch.float32, device=dev)  # (n == 0: empty, nothing to write)
-        with torch.cuda.device(dev):
-            heads.check(heads.lib().nmh_player_logits_backward(
-                ctypes.byref(ph), n, x.data_ptr(), stride, kind, rows, mask.data_ptr(), mstride, mkind,
-                g_out.data_ptr(), n_heads * (rows + 1), g_pq.data_ptr(), heads._stream()),
-                "nmh_player_logits_backward")
-        return None, g_pq, None, None, None, None
-
-
 def player_logits(ents: torch.Tensor, pq: torch.Tensor, mask_rows: torch.Tensor, mask_off, *, mask_kind=None,
                   set_rows=None) -> torch.Tensor:
     """The logits [N, len(mask_off) * (R + 1)] of up to four pointer heads over one entity set per
@@ -223,7 +143,7 @@ def player_logits(ents: torch.Tensor, pq: torch.Tensor, mask_rows: torch.Tensor,
     reference's zero padding row) are 0.0, and an entity no head allows is never read. The
     backward gives pq's gradient alone, without atomics: the same bits on every run. The entities
     and the mask must not be rewritten between forward and backward."""
-    return _PlayerLogits.apply(ents, pq, mask_rows, tuple(int(o) for o in mask_off), mask_kind, set_rows)
+    return _sets.SetLogits.apply(SPEC, ents, pq, mask_rows, tuple(int(o) for o in mask_off), 1, mask_kind, set_rows)
 
 
 class PlayerEncoder(nn.Module):

@@ -1,6 +1,9 @@
 """Compare one kernel's gfx950 ISA between two source trees (e.g. a round's tag and HEAD).
 
 Usage: python tools/isa_diff.py <tree_a> <tree_b> <file.hip> <mangled_kernel_a> [<mangled_kernel_b>]
+       python tools/isa_diff.py <tree_a> <tree_b> <file.hip> --all [<old>=<new> ...]
+--all compares every kernel of the file, one line each; <old>=<new> rewrites tree A's mangled names
+where a type was renamed (e.g. 12NmhItemHeads=11NmhSetHeads).
 Each tree is a directory holding nmmo_amd/csrc and include (git archive <rev> nmmo_amd/csrc include).
 Prints instruction / VGPR / SGPR / store / wait counts and the unified diff of the instruction
 streams with branch labels normalised (kernel-argument offsets show up as s_load offsets)."""
@@ -39,7 +42,25 @@ def stats(ins, vg, sg):
             f"ds {sum(v for k, v in c.items() if k.startswith('ds_'))}")
 
 
+def compare_all(ta, tb, src, renames):
+    sa, sb = asm(ta, src), asm(tb, src)
+    bad = 0
+    for ka in re.findall(r"\.amdhsa_kernel (\S+)", sa):
+        kb = ka
+        for old, new in renames:
+            kb = kb.replace(old, new)
+        (ia, va, ga), (ib, vb, gb) = kernel(sa, ka), kernel(sb, kb)
+        d = sum(1 for x in difflib.unified_diff(ia, ib, lineterm="", n=0) if x[:1] in "+-" and x[:3] not in ("+++", "---"))
+        bad += d != 0 or (va, ga) != (vb, gb)
+        print(f"{src} {kb}: instructions {len(ia)} -> {len(ib)}, differing lines {d}, vgpr {va} -> {vb}, sgpr {ga} -> {gb}")
+    nb = len(re.findall(r"\.amdhsa_kernel (\S+)", sb))
+    print(f"{src}: {nb} kernels in B, {bad} differ")
+    return bad
+
+
 def main():
+    if sys.argv[4] == "--all":
+        sys.exit(1 if compare_all(*sys.argv[1:4], [r.split("=") for r in sys.argv[5:]]) else 0)
     ta, tb, src, ka = sys.argv[1:5]
     kb = sys.argv[5] if len(sys.argv) > 5 else ka
     a, b = kernel(asm(ta, src), ka), kernel(asm(tb, src), kb)
