@@ -338,6 +338,29 @@ NMH_API int nmh_decoder_backward(const NmhHeads* hd, const NmhDecoderSets* sets,
                                  const float* head_entropy, const float* g_logprob, const float* g_entropy,
                                  float* g_dense, int64_t g_dense_stride, float* g_pq, void* stream);
 
+/* ---- Greedy selection (SPEC.md §24): the three forward calls above with the draw replaced by the
+ * argmax, for scoring a policy deterministically. Per head the action is the smallest index among
+ * the legal entries whose logit equals the head's maximum; a head with no legal entry gives action 0
+ * and contributes 0, as above. logprob, entropy, lse and head_entropy are, bit for bit, what the base
+ * call returns for actions_in = the actions_out of this one, and the matching *_backward takes them.
+ * Every other argument, check and limit is the base call's; there is no actions_in and no philox
+ * counter. The selection is a compile-time parameter of the kernels: the base calls run the code
+ * they ran before. n_rows == 0 is a no-op. */
+NMH_API int nmh_forward_argmax(const NmhHeads* hd, int32_t n_rows, const float* logits, int64_t logits_stride,
+                               const void* mask, int64_t mask_stride, int32_t mask_kind, int32_t* actions_out,
+                               float* logprob, float* entropy, float* lse, float* head_entropy, void* stream);
+
+NMH_API int nmh_pointer_forward_argmax(const NmhHeads* hd, const NmhPointer* pt, int32_t n_rows,
+                                       const float* queries, const float* const* keys, const float* dense,
+                                       int64_t dense_stride, const void* mask, int64_t mask_stride,
+                                       int32_t mask_kind, int32_t* actions_out, float* logprob, float* entropy,
+                                       float* lse, float* head_entropy, void* stream);
+
+NMH_API int nmh_decoder_forward_argmax(const NmhHeads* hd, const NmhDecoderSets* sets, int32_t n_rows,
+                                       const float* pq, const float* dense, int64_t dense_stride, const void* mask,
+                                       int64_t mask_stride, int32_t mask_kind, int32_t* actions_out, float* logprob,
+                                       float* entropy, float* lse, float* head_entropy, void* stream);
+
 NMH_API const char* nmh_last_error(void);
 /* "src=<hash of the sources the library was compiled from> arch=gfx950 fp_contract=off" */
 NMH_API const char* nmh_build_info(void);

@@ -5,6 +5,10 @@ parameter names and shapes, so that a start-kit policy `state_dict` loads with `
     agent = BaselineAgent(task_dim, hidden=256, fused_decoder=True, ...).cuda()
     action, logprob, entropy, value = agent(obs)                 # sample
     _, logprob, entropy, value = agent(obs, action=action)       # evaluate
+    action, logprob, entropy, value = agent(obs, greedy=True)    # select: every head's first maximum
+
+`RecurrentBaselineAgent` is the policy the start kit trains, `Recurrent(Baseline)`: this one as `policy`
+and an LSTM as `recurrent`, in the recurrent calling convention.
 
 The call convention is the stand-ins' of `nmmo_amd/trainer.py`, which `DeviceTrainer` takes: `obs` is
 the flat obs rows [N, obs_elems] float32, read through views and never written (the reference's tile
@@ -134,8 +138,12 @@ class BaselineAgent(nn.Module):
         return self._encode(obs)[0]
 
     # ---------------------------------------------------------------- decoder
-    def decode_actions(self, hidden: torch.Tensor, obs: torch.Tensor, action: torch.Tensor | None = None, emb=None):
-        """(action, logprob, entropy, value) of the hidden rows `hidden` of the rows `obs`."""
+    def decode_actions(self, hidden: torch.Tensor, obs: torch.Tensor, action: torch.Tensor | None = None, emb=None,
+                       greedy: bool = False):
+        """(action, logprob, entropy, value) of the hidden rows `hidden` of the rows `obs`. `greedy`:
+        select every head's first maximal legal entry instead of sampling (see `masked`)."""
+        if greedy and action is not None:
+            raise ValueError("greedy=True selects the actions: it cannot be combined with action=")
         layers = self.action_decoder.layers
         out = [layers[name](hidden) for name, _ in DECODER_LAYERS]
         dense = [out[k] for k, s in enumerate(self.head_set) if s < 0]
@@ -147,11 +155,11 @@ class BaselineAgent(nn.Module):
             sets = [(self.section(obs, "Entity"), "entity"), (self.section(obs, "Inventory"), "item"),
                     (self.section(obs, "Market"), "item")]
             acts, logp, ent = decoder_heads(torch.cat(dense, 1), self.pointer_slots(queries), sets, self.head_set, obs,
-                                            self.dims, action, seed=self.seed, offset=self.draws)
-            if action is None:
+                                            self.dims, action, seed=self.seed, offset=self.draws, greedy=greedy)
+            if action is None and not greedy:
                 self.draws += 1
             return acts, logp, ent, value
-        return (*self.masked(self.logits(out, queries, obs, emb), obs, action), value)
+        return (*self.masked(self.logits(out, queries, obs, emb), obs, action, greedy), value)
 
     def pointer_slots(self, queries) -> torch.Tensor:
         """pq [N, 8, 40]: the pointer heads' queries folded into the encoders' first layers, one
@@ -202,26 +210,100 @@ class BaselineAgent(nn.Module):
                     parts[k] = torch.matmul(padded, queries[k].unsqueeze(-1)).squeeze(-1)
         return torch.cat(parts, 1)
 
-    def masked(self, logits: torch.Tensor, obs: torch.Tensor, action: torch.Tensor | None = None):
-        """(action, logprob, entropy) of the heads' concatenated logits under the rows' ActionTargets."""
+    def masked(self, logits: torch.Tensor, obs: torch.Tensor, action: torch.Tensor | None = None,
+               greedy: bool = False):
+        """(action, logprob, entropy) of the heads' concatenated logits under the rows' ActionTargets.
+        `greedy` replaces the draw by the argmax of the masked logits, ties to the smallest index
+        (SPEC.md §24; what an evaluation run wants): deterministic, and `draws` does not advance."""
+        if greedy and action is not None:
+            raise ValueError("greedy=True selects the actions: it cannot be combined with action=")
         if self.fused_heads:
             from .heads import masked_heads
 
-            acts, logp, ent = masked_heads(logits, obs, self.dims, action, seed=self.seed, offset=self.draws)
-            if action is None:
+            acts, logp, ent = masked_heads(logits, obs, self.dims, action, seed=self.seed, offset=self.draws,
+                                           greedy=greedy)
+            if action is None and not greedy:
                 self.draws += 1
             return acts, logp, ent
         masks = obs[:, :self.mask_off[-1]] > 0
         acts, logp, ent = [], 0.0, 0.0
         for k in range(len(self.dims)):
             lo, hi = self.mask_off[k], self.mask_off[k + 1]
-            dist = torch.distributions.Categorical(logits=logits[:, lo:hi].masked_fill(~masks[:, lo:hi], -1e9))
-            a = dist.sample() if action is None else action[:, k]
+            filled = logits[:, lo:hi].masked_fill(~masks[:, lo:hi], -1e9)
+            dist = torch.distributions.Categorical(logits=filled)
+            if greedy:
+                a = filled.argmax(-1)  # the first maximum
+            else:
+                a = dist.sample() if action is None else action[:, k]
             acts.append(a)
             logp = logp + dist.log_prob(a)
             ent = ent + dist.entropy()
         return torch.stack(acts, 1), logp, ent
 
-    def forward(self, obs: torch.Tensor, action: torch.Tensor | None = None):
+    def forward(self, obs: torch.Tensor, action: torch.Tensor | None = None, greedy: bool = False):
         hidden, emb = self._encode(obs)
-        return self.decode_actions(hidden, obs, action, emb)
+        return self.decode_actions(hidden, obs, action, emb, greedy)
+
+
+class RecurrentBaselineAgent(nn.Module):
+    """The policy the start kit trains and evaluates, `Recurrent(Baseline)` (train.py:65-71,
+    evaluate.py:98-105, config.yaml:93-96): an LSTM between `encode_observations` and `decode_actions`.
+
+        agent = RecurrentBaselineAgent(task_dim, hidden=256, fused_lstm=True, fused_decoder=True).cuda()
+        action, logprob, entropy, value, state = agent(obs, state)              # sample, one step
+        _, logprob, entropy, value, state = agent(window, state, action=action)  # evaluate a bptt window
+        action, *_ = agent(obs, state, greedy=True)                              # select, for scoring
+
+    The submodules carry the names pufferlib's wrapper gives them, `policy` (a `BaselineAgent`, which
+    takes every keyword this class does not name) and `recurrent` (`lstm.LSTM`, SPEC.md §17, with
+    `fused_lstm`, else `torch.nn.LSTM`; both time-first), so that a start-kit checkpoint's
+    `state_dict`, keys `policy.*` and `recurrent.{weight_ih,weight_hh,bias_ih,bias_hh}_l{k}`, loads
+    whole with `strict=True` under either flag. `lstm` is `recurrent` under the name `DeviceTrainer`
+    looks for; it is a property, not a second registration. `recurrent` starts as the wrapper's does
+    [recalled: pufferlib 0.7.3 `RecurrentWrapper.__init__`, which is not importable here]: biases 0,
+    weights orthogonal with gain 1.0. `seed`, `draws` and `query_scale` are `policy`'s.
+
+    The calling convention is the wrapper's and `trainer.RecurrentMaskedAgent`'s: obs is [B, E] (one
+    step) or [B, T, E] (a window), the four outputs are flattened in (B, T) order, state is (h, c),
+    each [num_layers, B, hidden], or None for zeros. Under `torch.no_grad()` with `fused_lstm` a given
+    state is updated in place and returned."""
+
+    def __init__(self, task_dim: int = 2048, hidden: int = 256, num_layers: int = 1, fused_lstm: bool = False,
+                 **baseline_flags):
+        super().__init__()
+        self.fused_lstm = bool(fused_lstm)
+        self.policy = BaselineAgent(task_dim, hidden, **baseline_flags)
+        if self.fused_lstm:
+            from .lstm import LSTM
+
+            self.recurrent = LSTM(hidden, hidden, num_layers)  # hidden: a multiple of 64, or a ValueError
+        else:
+            self.recurrent = nn.LSTM(hidden, hidden, num_layers)
+        for name, p in self.recurrent.named_parameters():
+            if "bias" in name:
+                nn.init.constant_(p, 0.0)
+            else:
+                nn.init.orthogonal_(p, 1.0)
+
+    @property
+    def lstm(self):
+        return self.recurrent
+
+    seed = property(lambda self: self.policy.seed, lambda self, v: setattr(self.policy, "seed", int(v)))
+    draws = property(lambda self: self.policy.draws, lambda self, v: setattr(self.policy, "draws", int(v)))
+    query_scale = property(lambda self: self.policy.query_scale,
+                           lambda self, v: setattr(self.policy, "query_scale", float(v)))
+
+    def forward(self, obs: torch.Tensor, state=None, action: torch.Tensor | None = None, greedy: bool = False):
+        B, T = obs.shape[0], (obs.shape[1] if obs.dim() == 3 else 1)
+        flat = obs.reshape(B * T, obs.shape[-1])  # rows in (B, T) order; a view of a contiguous obs
+        hidden, emb = self.policy._encode(flat)
+        x = hidden.view(B, T, -1).transpose(0, 1)  # time first
+        if self.fused_lstm and state is not None and not torch.is_grad_enabled():
+            y, state = self.recurrent(x, state, out=state)
+        else:
+            y, state = self.recurrent(x, state)
+        hidden = y.transpose(0, 1).reshape(B * T, -1)
+        if action is not None:
+            action = action.reshape(B * T, -1)
+        return (*self.policy.decode_actions(hidden, flat, action, emb, greedy), state)

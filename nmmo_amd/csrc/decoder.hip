@@ -90,7 +90,8 @@ __device__ __forceinline__ const T* set_of(const DecPlan& pl, int set, int64_t r
   return static_cast<const T*>(pl.base[set]) + (r / pl.share[set]) * pl.stride[set];
 }
 
-template <typename T, int MK>
+// SEL (heads_dev.h): kDraw samples or evaluates actions_in; kArgmax selects greedily (SPEC.md §24)
+template <typename T, int MK, int SEL>
 __global__ __launch_bounds__(64 * kRowsPerBlock) void nmh_decoder_forward_kernel(
     DecPlan pl, int n_rows, int wave_bytes, const float* __restrict__ pq, const float* __restrict__ dense, int64_t ds,
     const void* __restrict__ mask, int64_t ms, const int32_t* __restrict__ actions_in, uint32_t seed_lo,
@@ -136,8 +137,8 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void nmh_decoder_forward_kernel
   }
   wave_sync();
   float lp = 0.f, ent = 0.f;
-  tile_heads(s, pl.dims, 0, pl.n_heads, pl.n_heads, r, true, actions_in, seed_lo, seed_hi, off_lo, off_hi, row_base,
-             actions_out, lse, head_entropy, lp, ent);
+  tile_heads<SEL>(s, pl.dims, 0, pl.n_heads, pl.n_heads, r, true, actions_in, seed_lo, seed_hi, off_lo, off_hi,
+                  row_base, actions_out, lse, head_entropy, lp, ent);
   if (lane == 0) {
     logprob[r] = lp;
     entropy[r] = ent;
@@ -286,17 +287,40 @@ int check_decoder(const char* fn, const NmhHeads* hd, const NmhDecoderSets* st, 
   return NMH_OK;
 }
 
-// launches K<element type, mask kind> on n_rows rows: 4 waves a workgroup where their LDS fits 64 KiB, else 2
+// launches K(element type, mask kind), one of the two kernel names below, on n_rows rows: 4 waves a
+// workgroup where their LDS fits 64 KiB, else 2
 #define DEC_LAUNCH(K, ...)                                                                              \
   do {                                                                                                  \
     const int rpb = kRowsPerBlock * wave_bytes <= kMaxLds ? kRowsPerBlock : 2;                          \
     const dim3 grid((unsigned)((n_rows + rpb - 1) / rpb)), block(64 * rpb);                             \
     hipStream_t hs = static_cast<hipStream_t>(stream);                                                  \
     const bool mf = mask_kind == NMH_MASK_F32;                                                          \
-    auto* kern = st->elem_kind == NMH_ELEM_F32 ? (mf ? K<float, NMH_MASK_F32> : K<float, NMH_MASK_U8>)   \
-                                               : (mf ? K<int16_t, NMH_MASK_F32> : K<int16_t, NMH_MASK_U8>); \
+    auto* kern = st->elem_kind == NMH_ELEM_F32 ? (mf ? K(float, NMH_MASK_F32) : K(float, NMH_MASK_U8))   \
+                                               : (mf ? K(int16_t, NMH_MASK_F32) : K(int16_t, NMH_MASK_U8)); \
     hipLaunchKernelGGL(kern, grid, block, (size_t)rpb* wave_bytes, hs, pl, n_rows, wave_bytes, __VA_ARGS__); \
   } while (0)
+#define DEC_FWD(T, MK) nmh_decoder_forward_kernel<T, MK, SEL>  // where a template's SEL is in scope
+#define DEC_BWD(T, MK) nmh_decoder_backward_kernel<T, MK>
+
+// nmh_decoder_forward (SEL = kDraw) and nmh_decoder_forward_argmax (kArgmax: no actions, no counter)
+template <int SEL>
+int decoder_forward(const char* fn, const NmhHeads* hd, const NmhDecoderSets* st, int32_t n_rows, const float* pq,
+                    const float* dense, int64_t dense_stride, const void* mask, int64_t mask_stride, int32_t mask_kind,
+                    const int32_t* actions_in, uint64_t seed, uint64_t offset, uint32_t row_base, int32_t* actions_out,
+                    float* logprob, float* entropy, float* lse, float* head_entropy, void* stream) {
+  DecPlan pl;
+  int wave_bytes;
+  int64_t dense_total;
+  const int rc = check_decoder(fn, hd, st, n_rows, pq, dense, dense_stride, mask, mask_stride, mask_kind, &pl,
+                               &wave_bytes, &dense_total);
+  if (rc != NMH_OK) return rc;
+  if (!actions_out || !logprob || !entropy || !lse || !head_entropy)
+    return heads_fail(NMH_E_INVALID, "%s: an output pointer is NULL", fn);
+  if (n_rows == 0) return NMH_OK;
+  DEC_LAUNCH(DEC_FWD, pq, dense, dense_stride, mask, mask_stride, actions_in, (uint32_t)seed, (uint32_t)(seed >> 32),
+             (uint32_t)offset, (uint32_t)(offset >> 32), row_base, actions_out, logprob, entropy, lse, head_entropy);
+  return heads_launched(fn);
+}
 
 }  // namespace
 
@@ -307,20 +331,18 @@ int nmh_decoder_forward(const NmhHeads* hd, const NmhDecoderSets* st, int32_t n_
                         int32_t mask_kind, const int32_t* actions_in, uint64_t seed, uint64_t offset,
                         uint32_t row_base, int32_t* actions_out, float* logprob, float* entropy, float* lse,
                         float* head_entropy, void* stream) {
-  const char* fn = "nmh_decoder_forward";
-  DecPlan pl;
-  int wave_bytes;
-  int64_t dense_total;
-  const int rc = check_decoder(fn, hd, st, n_rows, pq, dense, dense_stride, mask, mask_stride, mask_kind, &pl,
-                               &wave_bytes, &dense_total);
-  if (rc != NMH_OK) return rc;
-  if (!actions_out || !logprob || !entropy || !lse || !head_entropy)
-    return heads_fail(NMH_E_INVALID, "%s: an output pointer is NULL", fn);
-  if (n_rows == 0) return NMH_OK;
-  DEC_LAUNCH(nmh_decoder_forward_kernel, pq, dense, dense_stride, mask, mask_stride, actions_in, (uint32_t)seed,
-             (uint32_t)(seed >> 32), (uint32_t)offset, (uint32_t)(offset >> 32), row_base, actions_out, logprob,
-             entropy, lse, head_entropy);
-  return heads_launched(fn);
+  return decoder_forward<kDraw>("nmh_decoder_forward", hd, st, n_rows, pq, dense, dense_stride, mask, mask_stride,
+                                mask_kind, actions_in, seed, offset, row_base, actions_out, logprob, entropy, lse,
+                                head_entropy, stream);
+}
+
+int nmh_decoder_forward_argmax(const NmhHeads* hd, const NmhDecoderSets* st, int32_t n_rows, const float* pq,
+                               const float* dense, int64_t dense_stride, const void* mask, int64_t mask_stride,
+                               int32_t mask_kind, int32_t* actions_out, float* logprob, float* entropy, float* lse,
+                               float* head_entropy, void* stream) {
+  return decoder_forward<kArgmax>("nmh_decoder_forward_argmax", hd, st, n_rows, pq, dense, dense_stride, mask,
+                                  mask_stride, mask_kind, nullptr, 0, 0, 0, actions_out, logprob, entropy, lse,
+                                  head_entropy, stream);
 }
 
 int nmh_decoder_backward(const NmhHeads* hd, const NmhDecoderSets* st, int32_t n_rows, const float* pq,
@@ -344,7 +366,7 @@ int nmh_decoder_backward(const NmhHeads* hd, const NmhDecoderSets* st, int32_t n
   if (dense_total == 0) g_dense = nullptr;
   if (pl.n_ptr == 0) g_pq = nullptr;
   if (n_rows == 0 || (!g_dense && !g_pq)) return NMH_OK;
-  DEC_LAUNCH(nmh_decoder_backward_kernel, pq, dense, dense_stride, mask, mask_stride, actions, lse, head_entropy,
+  DEC_LAUNCH(DEC_BWD, pq, dense, dense_stride, mask, mask_stride, actions, lse, head_entropy,
              g_logprob, g_entropy, g_dense, g_dense_stride, g_pq);
   return heads_launched(fn);
 }

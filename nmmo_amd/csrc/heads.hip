@@ -31,8 +31,9 @@ namespace {
 constexpr int kRowsPerBlock = 4;
 constexpr int kStage = 16;  // staging loads in flight per lane and kind
 
-// tile: floats of LDS per wave = min(sum(dims), NMH_MAX_DIM), so any one head fits
-template <int MK>
+// tile: floats of LDS per wave = min(sum(dims), NMH_MAX_DIM), so any one head fits. SEL (heads_dev.h):
+// kDraw samples or evaluates actions_in; kArgmax selects greedily and ignores actions_in .. row_base.
+template <int MK, int SEL>
 __global__ __launch_bounds__(64 * kRowsPerBlock) void nmh_forward_kernel(
     NmhHeads hd, int n_rows, int tile, const float* __restrict__ logits, int64_t ls, const void* __restrict__ mask,
     int64_t ms, const int32_t* __restrict__ actions_in, uint32_t seed_lo, uint32_t seed_hi, uint32_t off_lo,
@@ -72,8 +73,8 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void nmh_forward_kernel(
       }
     }
     __syncthreads();
-    tile_heads(s, hd.dims, k0, k1, hd.n_heads, r, live, actions_in, seed_lo, seed_hi, off_lo, off_hi, row_base,
-               actions_out, lse, head_entropy, lp, ent);
+    tile_heads<SEL>(s, hd.dims, k0, k1, hd.n_heads, r, live, actions_in, seed_lo, seed_hi, off_lo, off_hi,
+                    row_base, actions_out, lse, head_entropy, lp, ent);
     off += len;
     k0 = k1;
   }
@@ -200,7 +201,7 @@ __device__ __forceinline__ void for_listed_keys(const uint16_t* list, int cnt, c
   }
 }
 
-template <int MK, int NC>
+template <int MK, int NC, int SEL>
 __global__ __launch_bounds__(64 * kRowsPerBlock) void nmh_pointer_forward_kernel(
     PtrPlan pl, int n_rows, int total, int wave_bytes, const float* __restrict__ queries,
     const float* __restrict__ dense, int64_t ds, const void* __restrict__ mask, int64_t ms,
@@ -235,8 +236,8 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void nmh_pointer_forward_kernel
   }
   wave_sync();
   float lp = 0.f, ent = 0.f;
-  tile_heads(s, pl.dims, 0, pl.n_heads, pl.n_heads, r, true, actions_in, seed_lo, seed_hi, off_lo, off_hi, row_base,
-             actions_out, lse, head_entropy, lp, ent);
+  tile_heads<SEL>(s, pl.dims, 0, pl.n_heads, pl.n_heads, r, true, actions_in, seed_lo, seed_hi, off_lo, off_hi,
+                  row_base, actions_out, lse, head_entropy, lp, ent);
   if (lane_id() == 0) {
     logprob[r] = lp;
     entropy[r] = ent;
@@ -400,19 +401,64 @@ int check_pointer(const char* fn, const NmhHeads* hd, const NmhPointer* pt, int3
   return NMH_OK;
 }
 
-// launches K<mask kind, 64-float chunks of a key row> on n_rows rows
+// launches K(mask kind, 64-float chunks of a key row), one of the two kernel names below, on n_rows rows
 #define NMH_POINTER_LAUNCH(K, fn, ...)                                                                           \
   do {                                                                                                           \
     const dim3 grid((unsigned)((n_rows + kRowsPerBlock - 1) / kRowsPerBlock)), block(64 * kRowsPerBlock);        \
     const int wave_bytes = wave_lds_bytes((int)total, max_rows), nc = (pl.key_dim + 63) / 64;                    \
     const bool f32 = mask_kind == NMH_MASK_F32;                                                                  \
-    auto* kern = nc <= 1   ? (f32 ? K<NMH_MASK_F32, 1> : K<NMH_MASK_U8, 1>)                                      \
-                 : nc == 2 ? (f32 ? K<NMH_MASK_F32, 2> : K<NMH_MASK_U8, 2>)                                      \
-                           : (f32 ? K<NMH_MASK_F32, 4> : K<NMH_MASK_U8, 4>);                                     \
+    auto* kern = nc <= 1   ? (f32 ? K(NMH_MASK_F32, 1) : K(NMH_MASK_U8, 1))                                      \
+                 : nc == 2 ? (f32 ? K(NMH_MASK_F32, 2) : K(NMH_MASK_U8, 2))                                      \
+                           : (f32 ? K(NMH_MASK_F32, 4) : K(NMH_MASK_U8, 4));                                     \
     hipLaunchKernelGGL(kern, grid, block, (size_t)kRowsPerBlock* wave_bytes, static_cast<hipStream_t>(stream), pl, \
                        n_rows, (int)total, wave_bytes, __VA_ARGS__);                                             \
     return heads_launched(fn);                                                                                   \
   } while (0)
+#define NMH_POINTER_FWD(MK, NC) nmh_pointer_forward_kernel<MK, NC, SEL>  // where a template's SEL is in scope
+#define NMH_POINTER_BWD(MK, NC) nmh_pointer_backward_kernel<MK, NC>
+
+// nmh_forward (SEL = kDraw) and nmh_forward_argmax (kArgmax, which passes no actions and no counter)
+template <int SEL>
+int forward(const char* fn, const NmhHeads* hd, int32_t n_rows, const float* logits, int64_t logits_stride,
+            const void* mask, int64_t mask_stride, int32_t mask_kind, const int32_t* actions_in, uint64_t seed,
+            uint64_t offset, uint32_t row_base, int32_t* actions_out, float* logprob, float* entropy, float* lse,
+            float* head_entropy, void* stream) {
+  int64_t total;
+  const int rc = check_args(fn, hd, n_rows, logits, logits_stride, mask, mask_stride, mask_kind, &total);
+  if (rc != NMH_OK) return rc;
+  if (!actions_out || !logprob || !entropy || !lse || !head_entropy)
+    return fail(NMH_E_INVALID, "%s: an output pointer is NULL", fn);
+  if (n_rows == 0) return NMH_OK;
+  const dim3 grid((unsigned)((n_rows + kRowsPerBlock - 1) / kRowsPerBlock)), block(64 * kRowsPerBlock);
+  auto* kern = mask_kind == NMH_MASK_F32 ? nmh_forward_kernel<NMH_MASK_F32, SEL> : nmh_forward_kernel<NMH_MASK_U8, SEL>;
+  const int tile = (int)std::min<int64_t>(total, NMH_MAX_DIM);
+  hipLaunchKernelGGL(kern, grid, block, sizeof(float) * kRowsPerBlock * tile, static_cast<hipStream_t>(stream), *hd,
+                     n_rows, tile, logits, logits_stride, mask, mask_stride, actions_in, (uint32_t)seed,
+                     (uint32_t)(seed >> 32), (uint32_t)offset, (uint32_t)(offset >> 32), row_base, actions_out,
+                     logprob, entropy, lse, head_entropy);
+  return heads_launched(fn);
+}
+
+// nmh_pointer_forward and nmh_pointer_forward_argmax likewise
+template <int SEL>
+int pointer_forward(const char* fn, const NmhHeads* hd, const NmhPointer* pt, int32_t n_rows, const float* queries,
+                    const float* const* keys, const float* dense, int64_t dense_stride, const void* mask,
+                    int64_t mask_stride, int32_t mask_kind, const int32_t* actions_in, uint64_t seed, uint64_t offset,
+                    uint32_t row_base, int32_t* actions_out, float* logprob, float* entropy, float* lse,
+                    float* head_entropy, void* stream) {
+  PtrPlan pl;
+  int64_t total, dense_total;
+  int max_rows;
+  const int rc = check_pointer(fn, hd, pt, n_rows, queries, keys, dense, dense_stride, mask, mask_stride, mask_kind,
+                               &pl, &total, &dense_total, &max_rows);
+  if (rc != NMH_OK) return rc;
+  if (!actions_out || !logprob || !entropy || !lse || !head_entropy)
+    return fail(NMH_E_INVALID, "%s: an output pointer is NULL", fn);
+  if (n_rows == 0) return NMH_OK;
+  NMH_POINTER_LAUNCH(NMH_POINTER_FWD, fn, queries, dense, dense_stride, mask, mask_stride, actions_in, (uint32_t)seed,
+                     (uint32_t)(seed >> 32), (uint32_t)offset, (uint32_t)(offset >> 32), row_base, actions_out,
+                     logprob, entropy, lse, head_entropy);
+}
 
 }  // namespace
 
@@ -441,19 +487,15 @@ int nmh_forward(const NmhHeads* hd, int32_t n_rows, const float* logits, int64_t
                 int64_t mask_stride, int32_t mask_kind, const int32_t* actions_in, uint64_t seed, uint64_t offset,
                 uint32_t row_base, int32_t* actions_out, float* logprob, float* entropy, float* lse,
                 float* head_entropy, void* stream) {
-  int64_t total;
-  const int rc = check_args("nmh_forward", hd, n_rows, logits, logits_stride, mask, mask_stride, mask_kind, &total);
-  if (rc != NMH_OK) return rc;
-  if (!actions_out || !logprob || !entropy || !lse || !head_entropy)
-    return fail(NMH_E_INVALID, "nmh_forward: an output pointer is NULL");
-  if (n_rows == 0) return NMH_OK;
-  const dim3 grid((unsigned)((n_rows + kRowsPerBlock - 1) / kRowsPerBlock)), block(64 * kRowsPerBlock);
-  auto* kern = mask_kind == NMH_MASK_F32 ? nmh_forward_kernel<NMH_MASK_F32> : nmh_forward_kernel<NMH_MASK_U8>;
-  const int tile = (int)std::min<int64_t>(total, NMH_MAX_DIM);
-  hipLaunchKernelGGL(kern, grid, block, sizeof(float) * kRowsPerBlock * tile, static_cast<hipStream_t>(stream), *hd,
-                     n_rows, tile, logits, logits_stride, mask, mask_stride, actions_in, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)offset,
-                     (uint32_t)(offset >> 32), row_base, actions_out, logprob, entropy, lse, head_entropy);
-  return heads_launched("nmh_forward");
+  return forward<kDraw>("nmh_forward", hd, n_rows, logits, logits_stride, mask, mask_stride, mask_kind, actions_in,
+                        seed, offset, row_base, actions_out, logprob, entropy, lse, head_entropy, stream);
+}
+
+int nmh_forward_argmax(const NmhHeads* hd, int32_t n_rows, const float* logits, int64_t logits_stride,
+                       const void* mask, int64_t mask_stride, int32_t mask_kind, int32_t* actions_out, float* logprob,
+                       float* entropy, float* lse, float* head_entropy, void* stream) {
+  return forward<kArgmax>("nmh_forward_argmax", hd, n_rows, logits, logits_stride, mask, mask_stride, mask_kind,
+                          nullptr, 0, 0, 0, actions_out, logprob, entropy, lse, head_entropy, stream);
 }
 
 int nmh_backward(const NmhHeads* hd, int32_t n_rows, const float* logits, int64_t logits_stride, const void* mask,
@@ -480,18 +522,18 @@ int nmh_pointer_forward(const NmhHeads* hd, const NmhPointer* pt, int32_t n_rows
                         int64_t mask_stride, int32_t mask_kind, const int32_t* actions_in, uint64_t seed,
                         uint64_t offset, uint32_t row_base, int32_t* actions_out, float* logprob, float* entropy,
                         float* lse, float* head_entropy, void* stream) {
-  PtrPlan pl;
-  int64_t total, dense_total;
-  int max_rows;
-  const int rc = check_pointer("nmh_pointer_forward", hd, pt, n_rows, queries, keys, dense, dense_stride, mask,
-                               mask_stride, mask_kind, &pl, &total, &dense_total, &max_rows);
-  if (rc != NMH_OK) return rc;
-  if (!actions_out || !logprob || !entropy || !lse || !head_entropy)
-    return fail(NMH_E_INVALID, "nmh_pointer_forward: an output pointer is NULL");
-  if (n_rows == 0) return NMH_OK;
-  NMH_POINTER_LAUNCH(nmh_pointer_forward_kernel, "nmh_pointer_forward", queries, dense, dense_stride, mask,
-                     mask_stride, actions_in, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)offset,
-                     (uint32_t)(offset >> 32), row_base, actions_out, logprob, entropy, lse, head_entropy);
+  return pointer_forward<kDraw>("nmh_pointer_forward", hd, pt, n_rows, queries, keys, dense, dense_stride, mask,
+                                mask_stride, mask_kind, actions_in, seed, offset, row_base, actions_out, logprob,
+                                entropy, lse, head_entropy, stream);
+}
+
+int nmh_pointer_forward_argmax(const NmhHeads* hd, const NmhPointer* pt, int32_t n_rows, const float* queries,
+                               const float* const* keys, const float* dense, int64_t dense_stride, const void* mask,
+                               int64_t mask_stride, int32_t mask_kind, int32_t* actions_out, float* logprob,
+                               float* entropy, float* lse, float* head_entropy, void* stream) {
+  return pointer_forward<kArgmax>("nmh_pointer_forward_argmax", hd, pt, n_rows, queries, keys, dense, dense_stride,
+                                  mask, mask_stride, mask_kind, nullptr, 0, 0, 0, actions_out, logprob, entropy, lse,
+                                  head_entropy, stream);
 }
 
 int nmh_pointer_backward(const NmhHeads* hd, const NmhPointer* pt, int32_t n_rows, const float* queries,
@@ -521,7 +563,7 @@ int nmh_pointer_backward(const NmhHeads* hd, const NmhPointer* pt, int32_t n_row
   if (dense_total == 0) g_dense = nullptr;
   if (pl.n_ptr == 0) g_queries = nullptr;
   if (n_rows == 0) return NMH_OK;
-  NMH_POINTER_LAUNCH(nmh_pointer_backward_kernel, "nmh_pointer_backward", queries, dense, dense_stride, mask,
+  NMH_POINTER_LAUNCH(NMH_POINTER_BWD, "nmh_pointer_backward", queries, dense, dense_stride, mask,
                      mask_stride, actions, lse, head_entropy, g_logprob, g_entropy, g_dense, g_dense_stride,
                      g_queries, gk);
 }

@@ -48,22 +48,36 @@ struct HeadOut {
   float logprob, lse, entropy;
 };
 
+// How a forward kernel chooses a head's action, a compile-time parameter of the kernel. kDraw is
+// one instantiation for both of the calls that have `actions_in`: NULL samples, else it is evaluated.
+// kArgmax is the greedy selection of SPEC.md §24; it reads neither actions_in nor the philox counter.
+enum Select { kDraw = 0, kArgmax = 1 };
+
 // One head of one row on one wave (all 64 lanes active) from its staged copy s[0, n): the logit
 // where legal, -inf where not. Lane l owns entries [l c, min(n, (l + 1) c)); c is odd, so the
-// lanes' reads s[l c + j] fall on distinct LDS banks. `sample`: draw with u, else evaluate a_in.
+// lanes' reads s[l c + j] fall on distinct LDS banks. kDraw: `sample` draws with u, else a_in is
+// evaluated. kArgmax: the smallest index whose logit is the head's maximum (0 if nothing is legal),
+// then evaluated like a given action; sample, u and a_in are not looked at.
+template <int SEL>
 __device__ __forceinline__ HeadOut head_forward(const float* s, int n, bool sample, float u, int a_in) {
   const int c = ((n + 63) >> 6) | 1;
   const int lo = min(n, lane_id() * c), hi = min(n, lo + c);
   float m = -INFINITY;
-  for (int i = lo; i < hi; i++) m = fmaxf(m, s[i]);
+  int first = lo;  // kArgmax: the lane's first index of its maximum
+  for (int i = lo; i < hi; i++) {
+    const float x = s[i];
+    if (SEL == kArgmax) first = x > m ? i : first;
+    m = fmaxf(m, x);
+  }
   const uint64_t has = __ballot(m != -INFINITY);  // lanes that own a legal entry
   HeadOut o;
   if (has == 0) {  // empty legal set: contributes nothing; a sampled action is uniform over n
-    o.action = sample ? min(n - 1, (int)(u * (float)n)) : a_in;
+    o.action = SEL == kArgmax ? 0 : sample ? min(n - 1, (int)(u * (float)n)) : a_in;
     o.logprob = o.lse = o.entropy = 0.f;
     return o;
   }
   const bool mine = m != -INFINITY;
+  const float lane_max = m;
   m = wave_max_f(m);
   float sum = 0.f, ts = 0.f;
   for (int i = lo; i < hi; i++) {
@@ -80,7 +94,13 @@ __device__ __forceinline__ HeadOut head_forward(const float* s, int n, bool samp
   o.lse = m + logS;
   o.entropy = logS - T / S;  // = lse - sum p x, without the cancellation against m
   int a = a_in;
-  if (sample) {
+  if (SEL == kArgmax) {
+    // Lanes own ascending ranges, so the lowest lane whose maximum is the wave's holds the smallest
+    // index. fmaxf returns one of its operands: some lane's maximum equals m bit for bit (a NaN logit
+    // is outside the contract; lane 0's index keeps the action in range then).
+    const uint64_t top = __ballot(mine && lane_max == m);
+    a = __builtin_amdgcn_readlane(first, top ? __ffsll((unsigned long long)top) - 1 : 0);
+  } else if (sample) {
     const float tgt = u * S;
     // first lane with a legal entry whose inclusive sum passes tgt; u * S can round up to S, and
     // the scan's lane sums are not exactly monotone, so fall back to the last lane that has one
@@ -105,15 +125,16 @@ __device__ __forceinline__ HeadOut head_forward(const float* s, int n, bool samp
   return o;
 }
 
-// Heads [k0, k1) of row r from their staged copies, which lie back to back from s: draws or reads
-// the action of each, stores its per-head outputs (a live wave's lane 0) and adds its logprob and
-// entropy to lp / ent.
+// Heads [k0, k1) of row r from their staged copies, which lie back to back from s: draws, reads or
+// (kArgmax) selects the action of each, stores its per-head outputs (a live wave's lane 0) and adds
+// its logprob and entropy to lp / ent.
+template <int SEL>
 __device__ __forceinline__ void tile_heads(const float* s, const int32_t* dims, int k0, int k1, int n_heads, int64_t r,
                                            bool live, const int32_t* __restrict__ actions_in, uint32_t seed_lo,
                                            uint32_t seed_hi, uint32_t off_lo, uint32_t off_hi, uint32_t row_base,
                                            int32_t* __restrict__ actions_out, float* __restrict__ lse,
                                            float* __restrict__ head_entropy, float& lp, float& ent) {
-  const bool sample = actions_in == nullptr;
+  const bool sample = SEL == kDraw && actions_in == nullptr;
   int o_s = 0;
   for (int k = k0; k < k1; k++) {
     const int n = dims[k];
@@ -121,10 +142,10 @@ __device__ __forceinline__ void tile_heads(const float* s, const int32_t* dims, 
     int a_in = 0;
     if (sample) {
       u = (float)(philox(row_base + (uint32_t)r, (uint32_t)k, off_lo, off_hi, seed_lo, seed_hi).x >> 8) * 0x1p-24f;
-    } else {
+    } else if (SEL == kDraw) {
       a_in = actions_in[r * n_heads + k];
     }
-    const HeadOut o = head_forward(s + o_s, n, sample, u, a_in);
+    const HeadOut o = head_forward<SEL>(s + o_s, n, sample, u, a_in);
     lp += o.logprob;
     ent += o.entropy;
     if (live && lane_id() == 0) {

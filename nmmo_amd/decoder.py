@@ -74,6 +74,9 @@ def _make_function():
     class DecoderHeads(torch.autograd.Function):
         @staticmethod
         def forward(ctx, dense, pq, mask, dims, head_set, action, seed, offset, row_base, meta, *set_tensors):
+            # the selection mode, a bool, is the last argument where one is given (after the set tensors)
+            greedy = bool(set_tensors) and isinstance(set_tensors[-1], bool) and set_tensors[-1]
+            set_tensors = [t for t in set_tensors if not isinstance(t, bool)]
             hd = heads.heads_struct(dims)
             dims, head_set = [int(d) for d in dims], [int(s) for s in head_set]
             if len(head_set) != len(dims):
@@ -117,9 +120,9 @@ def _make_function():
             a_in, (a_out, logprob, entropy, lse, hent), io = heads.head_io(action, n, hd.n_heads, dev, seed, offset,
                                                                           row_base)
             with torch.cuda.device(dev):
-                heads.check(heads.lib().nmh_decoder_forward(
-                    ctypes.byref(hd), ctypes.byref(st), n, heads.ptr(pq), heads.ptr(dense), d_stride, mptr, mstride,
-                    mkind, *io, heads._stream()), "nmh_decoder_forward")
+                heads.forward_call("nmh_decoder_forward", greedy,
+                                   (ctypes.byref(hd), ctypes.byref(st), n, heads.ptr(pq), heads.ptr(dense), d_stride,
+                                    mptr, mstride, mkind), io)
             ctx.args = (hd, st, mstride, mkind, d_stride, n_dense, n_ptr)
             ctx.has = (dense is not None, pq is not None)
             ctx.set_materialize_grads(False)  # an unused logprob / entropy arrives as None -> NULL
@@ -145,7 +148,7 @@ def _make_function():
                     ctypes.byref(hd), ctypes.byref(st), n, ptr(pq), ptr(dense), d_stride, mask.data_ptr(), mstride,
                     mkind, actions.data_ptr(), lse.data_ptr(), hent.data_ptr(), ptr(glp), ptr(gen), ptr(g_d), n_dense,
                     ptr(g_q), heads._stream()), "nmh_decoder_backward")
-            return (g_d, g_q, None, None, None, None, None, None, None, None, *[None] * len(rest))
+            return (g_d, g_q, *[None] * (len(need) - 2))  # the sets, and the mode where it was passed
 
     return DecoderHeads
 
@@ -154,21 +157,22 @@ _function = None
 
 
 def decoder_heads_full(dense, pq, sets, head_set, mask, dims, action=None, *, seed: int = 0, offset: int = 0,
-                       row_base: int = 0):
+                       row_base: int = 0, greedy: bool = False):
     """`decoder_heads` plus the per-head saved values: (action, logprob, entropy, lse [N, H],
     head_entropy [N, H])."""
     global _function
+    heads.check_greedy(greedy, action)
     if _function is None:
         _function = _make_function()
     split = _split_sets(sets, dims, head_set)
     a, logprob, entropy, lse, hent = _function.apply(
         dense, pq, mask, tuple(dims), tuple(head_set), action, seed, offset, row_base,
-        tuple((rule, share, rows) for _, rule, share, rows in split), *[t for t, _, _, _ in split])
+        tuple((rule, share, rows) for _, rule, share, rows in split), *[t for t, _, _, _ in split], bool(greedy))
     return (a if action is None else action), logprob, entropy, lse, hent
 
 
 def decoder_heads(dense, pq, sets, head_set, mask, dims, action=None, *, seed: int = 0, offset: int = 0,
-                  row_base: int = 0):
+                  row_base: int = 0, greedy: bool = False):
     """Every masked categorical head of a batch of obs rows in one kernel, the pointer heads' logits
     taken from the candidates' own columns (SPEC.md §23).
 
@@ -183,11 +187,11 @@ def decoder_heads(dense, pq, sets, head_set, mask, dims, action=None, *, seed: i
         [M, >= cols R] view; obs row r reads set r // share. A set is read in place through its own
         pointer and stride and never copied or written; candidates that a head's mask forbids are
         never addressed.
-    mask, action, seed, offset, row_base: as for `masked_heads`.
+    mask, action, seed, offset, row_base, greedy: as for `masked_heads`.
     Returns (action, logprob [N], entropy [N]), bit for bit what `masked_heads` returns on the
     logits `item_logits` / `player_logits` would make. logprob and entropy are differentiable with
     respect to dense and pq; a gradient nothing requires is not computed. A call allocates its
     outputs and nothing else. The sets and the mask must not be rewritten between forward and
     backward."""
     return decoder_heads_full(dense, pq, sets, head_set, mask, dims, action, seed=seed, offset=offset,
-                              row_base=row_base)[:3]
+                              row_base=row_base, greedy=greedy)[:3]

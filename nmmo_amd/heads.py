@@ -3,6 +3,7 @@
 
     action, logprob, entropy = masked_heads(logits, obs, dims)            # sample
     _, logprob, entropy = masked_heads(logits, obs, dims, action=action)  # evaluate, differentiable
+    action, logprob, entropy = masked_heads(logits, obs, dims, greedy=True)  # select the argmax (SPEC.md §24)
 
 replaces the per-head `masked_fill(mask == 0, -1e9)` + `Categorical` loop of the reference's
 policies (baseline_policy.py:245-262) by one kernel forward and one backward. `pointer_heads`
@@ -25,7 +26,8 @@ LIB_PATH = os.environ.get("NMMO_HEADS_LIB", build.lib_path("heads"))
 SYMBOLS = ["nmh_forward", "nmh_backward", "nmh_pointer_forward", "nmh_pointer_backward", "nmh_tile_forward",
            "nmh_tile_backward", "nmh_tile2_forward", "nmh_tile2_backward", "nmh_item_features", "nmh_item_logits",
            "nmh_item_logits_backward", "nmh_player_features", "nmh_player_logits", "nmh_player_logits_backward",
-           "nmh_decoder_forward", "nmh_decoder_backward", "nmh_last_error", "nmh_build_info"]
+           "nmh_decoder_forward", "nmh_decoder_backward", "nmh_forward_argmax", "nmh_pointer_forward_argmax",
+           "nmh_decoder_forward_argmax", "nmh_last_error", "nmh_build_info"]
 MAX_HEADS, MAX_DIM = 16, 2048
 MAX_SETS, MAX_KEY_DIM = 4, 256
 MASK_F32, MASK_U8 = 0, 1
@@ -68,6 +70,10 @@ def declare(L):
     L.nmh_decoder_forward.argtypes = [hp, vp, i32, vp, vp, i64, vp, i64, i32, vp, u64, u64, ctypes.c_uint32,
                                       vp, vp, vp, vp, vp, vp]  # nmmo_amd/decoder.py
     L.nmh_decoder_backward.argtypes = [hp, vp, i32, vp, vp, i64, vp, i64, i32, vp, vp, vp, vp, vp, vp, i64, vp, vp]
+    # greedy selection (SPEC.md §24): the forwards without actions_in, seed, offset and row_base
+    L.nmh_forward_argmax.argtypes = [hp, i32, vp, i64, vp, i64, i32, vp, vp, vp, vp, vp, vp]
+    L.nmh_pointer_forward_argmax.argtypes = [hp, pp, i32, vp, kp, vp, i64, vp, i64, i32, vp, vp, vp, vp, vp, vp]
+    L.nmh_decoder_forward_argmax.argtypes = [hp, vp, i32, vp, vp, i64, vp, i64, i32, vp, vp, vp, vp, vp, vp]
 
 
 def lib():
@@ -152,12 +158,24 @@ def head_io(action, n: int, n_heads: int, dev, seed, offset, row_base):
         hent.data_ptr())
 
 
+def check_greedy(greedy: bool, action):
+    if greedy and action is not None:
+        raise ValueError("greedy=True selects the actions: it cannot be combined with action=")
+
+
+def forward_call(name: str, greedy: bool, args, io):
+    """The forward `name` on the current stream, or with `greedy` its `_argmax` twin (SPEC.md §24),
+    which takes the same arguments without `head_io`'s actions_in, seed, offset and row_base."""
+    fn = f"{name}_argmax" if greedy else name
+    check(getattr(lib(), fn)(*args, *(io[4:] if greedy else io), _stream()), fn)
+
+
 def _make_function():
     import torch
 
     class MaskedHeads(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, logits, mask, dims, action, seed, offset, row_base):
+        def forward(ctx, logits, mask, dims, action, seed, offset, row_base, greedy=False):
             hd = heads_struct(dims)
             total = sum(hd.dims[:hd.n_heads])
             if not logits.is_cuda or not mask.is_cuda:
@@ -170,8 +188,8 @@ def _make_function():
             dev = logits.device
             a_in, (a_out, logprob, entropy, lse, hent), io = head_io(action, n, hd.n_heads, dev, seed, offset, row_base)
             with torch.cuda.device(dev):
-                check(lib().nmh_forward(ctypes.byref(hd), n, logits.data_ptr(), lstride, mptr, mstride, kind, *io,
-                                        _stream()), "nmh_forward")
+                forward_call("nmh_forward", greedy,
+                             (ctypes.byref(hd), n, logits.data_ptr(), lstride, mptr, mstride, kind), io)
             ctx.hd, ctx.kind = hd, kind
             ctx.set_materialize_grads(False)  # an unused logprob / entropy arrives as None -> NULL
             ctx.save_for_backward(logits, mask, a_out, lse, hent)
@@ -191,7 +209,7 @@ def _make_function():
                     ctypes.byref(hd), n, logits.data_ptr(), max(logits.stride(0), total), mask.data_ptr(),
                     max(mask.stride(0), total), ctx.kind, actions.data_ptr(), lse.data_ptr(), hent.data_ptr(),
                     ptr(glp), ptr(gen), g_logits.data_ptr(), total, _stream()), "nmh_backward")
-            return g_logits, None, None, None, None, None, None
+            return g_logits, None, None, None, None, None, None, None
 
     return MaskedHeads
 
@@ -199,17 +217,21 @@ def _make_function():
 _function = None
 
 
-def masked_heads_full(logits, mask, dims, action=None, *, seed: int = 0, offset: int = 0, row_base: int = 0):
+def masked_heads_full(logits, mask, dims, action=None, *, seed: int = 0, offset: int = 0, row_base: int = 0,
+                      greedy: bool = False):
     """`masked_heads` plus the per-head saved values: (action, logprob, entropy, lse [N, H],
     head_entropy [N, H])."""
     global _function
+    check_greedy(greedy, action)
     if _function is None:
         _function = _make_function()
-    a, logprob, entropy, lse, hent = _function.apply(logits, mask, tuple(dims), action, seed, offset, row_base)
+    a, logprob, entropy, lse, hent = _function.apply(logits, mask, tuple(dims), action, seed, offset, row_base,
+                                                     bool(greedy))
     return (a if action is None else action), logprob, entropy, lse, hent
 
 
-def masked_heads(logits, mask, dims, action=None, *, seed: int = 0, offset: int = 0, row_base: int = 0):
+def masked_heads(logits, mask, dims, action=None, *, seed: int = 0, offset: int = 0, row_base: int = 0,
+                 greedy: bool = False):
     """All masked categorical heads of a batch of rows in one kernel (SPEC.md §15).
 
     logits: float32 [N, sum(dims)] on the GPU, the heads' logits concatenated.
@@ -218,10 +240,15 @@ def masked_heads(logits, mask, dims, action=None, *, seed: int = 0, offset: int 
     action: None samples (int32 [N, H]; row r, head k draws from the philox counter
         (row_base + r, k, offset) under `seed`: the caller advances `offset` per call); else the
         given [N, H] actions are evaluated and returned as they are.
+    greedy: with action None, select instead of sampling (SPEC.md §24): per head the smallest legal
+        index whose logit is the head's maximum, 0 if nothing is legal; seed, offset and row_base
+        are not used. logprob and entropy are those of evaluating the returned actions, and
+        differentiable in the same way. With an action it is a ValueError.
     Returns (action, logprob [N], entropy [N]); logprob and entropy are sums over heads and
     differentiable with respect to logits.
     """
-    return masked_heads_full(logits, mask, dims, action, seed=seed, offset=offset, row_base=row_base)[:3]
+    return masked_heads_full(logits, mask, dims, action, seed=seed, offset=offset, row_base=row_base,
+                             greedy=greedy)[:3]
 
 
 # ---------------------------------------------------------------- pointer heads (SPEC.md §18)
@@ -267,6 +294,9 @@ def _make_pointer_function():
     class PointerHeads(torch.autograd.Function):
         @staticmethod
         def forward(ctx, queries, dense, mask, dims, head_set, action, seed, offset, row_base, *keys):
+            # the selection mode, a bool, is the last argument where one is given (after the key tensors)
+            greedy = bool(keys) and isinstance(keys[-1], bool) and keys[-1]
+            keys = [kt for kt in keys if not isinstance(kt, bool)]
             hd = heads_struct(dims)
             dims, head_set = [int(d) for d in dims], [int(s) for s in head_set]
             if len(head_set) != len(dims):
@@ -303,9 +333,9 @@ def _make_pointer_function():
             mask, mptr, mstride, kind = _mask_arg(mask, n, total)
             a_in, (a_out, logprob, entropy, lse, hent), io = head_io(action, n, hd.n_heads, dev, seed, offset, row_base)
             with torch.cuda.device(dev):
-                check(lib().nmh_pointer_forward(
-                    ctypes.byref(hd), ctypes.byref(pt), n, ptr(queries), _key_array(keys), ptr(dense), n_dense, mptr,
-                    mstride, kind, *io, _stream()), "nmh_pointer_forward")
+                forward_call("nmh_pointer_forward", greedy,
+                             (ctypes.byref(hd), ctypes.byref(pt), n, ptr(queries), _key_array(keys), ptr(dense),
+                              n_dense, mptr, mstride, kind), io)
             ctx.hd, ctx.pt, ctx.kind, ctx.n_dense = hd, pt, kind, n_dense
             ctx.has = (queries is not None, dense is not None)
             ctx.set_materialize_grads(False)
@@ -333,7 +363,8 @@ def _make_pointer_function():
                     mask.data_ptr(), max(mask.stride(0), total), ctx.kind, actions.data_ptr(), lse.data_ptr(),
                     hent.data_ptr(), ptr(glp), ptr(gen), ptr(g_d), ctx.n_dense, ptr(g_q), _key_array(g_k), _stream()),
                     "nmh_pointer_backward")
-            return (g_q, g_d, None, None, None, None, None, None, None, *g_k)
+            return (g_q, g_d, None, None, None, None, None, None, None, *g_k,
+                    *[None] * (len(ctx.needs_input_grad) - 9 - len(g_k)))  # the mode, where it was passed
 
     return PointerHeads
 
@@ -342,19 +373,20 @@ _pointer_function = None
 
 
 def pointer_heads_full(queries, keys, head_set, dense_logits, mask, dims, action=None, *, seed: int = 0,
-                       offset: int = 0, row_base: int = 0):
+                       offset: int = 0, row_base: int = 0, greedy: bool = False):
     """`pointer_heads` plus the per-head saved values: (action, logprob, entropy, lse [N, H],
     head_entropy [N, H])."""
     global _pointer_function
+    check_greedy(greedy, action)
     if _pointer_function is None:
         _pointer_function = _make_pointer_function()
     a, logprob, entropy, lse, hent = _pointer_function.apply(
-        queries, dense_logits, mask, tuple(dims), tuple(head_set), action, seed, offset, row_base, *keys)
+        queries, dense_logits, mask, tuple(dims), tuple(head_set), action, seed, offset, row_base, *keys, bool(greedy))
     return (a if action is None else action), logprob, entropy, lse, hent
 
 
 def pointer_heads(queries, keys, head_set, dense_logits, mask, dims, action=None, *, seed: int = 0, offset: int = 0,
-                  row_base: int = 0):
+                  row_base: int = 0, greedy: bool = False):
     """Masked categorical heads of which some are pointer heads, in one kernel (SPEC.md §18): the
     decoders of the reference's policies (baseline_policy.py:222-230) without the zero-padded copy
     of the embeddings, the batched mat-vec over every candidate and the logits tensor.
@@ -366,10 +398,10 @@ def pointer_heads(queries, keys, head_set, dense_logits, mask, dims, action=None
     keys: a sequence of float32 [N, m_s, D]. Head k's logit of candidate j < m_s is
         keys[s][r, j] . queries[r, p]; rows of illegal candidates are never read.
     dense_logits: float32 [N, sum of the dense heads' dims] in head order, or None.
-    mask, action, seed, offset, row_base: as for `masked_heads`; mask columns cover all heads.
+    mask, action, seed, offset, row_base, greedy: as for `masked_heads`; mask columns cover all heads.
     Returns (action, logprob [N], entropy [N]); logprob and entropy are differentiable with respect
     to queries, every keys tensor and dense_logits, and a gradient that nothing requires is not
     computed. Non-contiguous or misaligned inputs are copied; there is no torch fallback.
     """
     return pointer_heads_full(queries, keys, head_set, dense_logits, mask, dims, action, seed=seed, offset=offset,
-                              row_base=row_base)[:3]
+                              row_base=row_base, greedy=greedy)[:3]
