@@ -282,6 +282,60 @@ NMH_API int nmh_player_logits_backward(const NmhPlayerHeads* ph, int32_t n_rows,
                                        int64_t mask_stride, int32_t mask_kind, const float* g_out,
                                        int64_t g_stride, float* g_pq, void* stream);
 
+/* ---- Embedded sets (SPEC.md §25): the takeru policy's ReducedPlayerEncoder and ReducedItemEncoder
+ * are a linear layer over cat(E[idx_0], .., E[idx_{D-1}], x_0 / s_0, .., x_{C-1} / s_{C-1}) of a
+ * candidate's columns: D discrete columns, idx_d = clip(trunc(x + off_d), 0, 255) with NaN giving 0,
+ * and C continuous columns, x / s being one IEEE float32 division. The calls hold no parameters: the
+ * caller folds a head's query into a score table pq (below) and reads back the table's gradient.
+ *   NMH_EMBED_ENTITY: 31 columns. Discrete: columns 0, 1, 8, 10 with off 0, 256, 512, 768 (so the last
+ *     three read bin 255 for every value >= -1, -257, -513). Continuous: columns 2..7, 9, 11..30 with
+ *     s = 256, 256, 100, 1024, 3, 50, 1024, 100, 100, 100, 100, then (10, 100) seven times, then 100, 10.
+ *   NMH_EMBED_ITEM: 16 columns. Discrete: columns 1, 14 with off 2, 0. Continuous: columns 3..13, 15
+ *     with s = 10, 10, 10, 100, 100, 100, 40, 40, 40, 100, 100, 100.
+ * Element kinds are NMH_ELEM_F32 / NMH_ELEM_I16; an int16 element is converted exactly first. */
+#define NMH_EMBED_ENTITY 0
+#define NMH_EMBED_ITEM 1
+#define NMH_EMBED_BINS 256           /* table rows an index can reach */
+#define NMH_EMBED_ENTITY_QUERY 1052  /* floats per score table: 4 x 256 bins, 27 weights, the bias */
+#define NMH_EMBED_ITEM_QUERY 528     /* 2 x 256 bins, 12 weights, the bias, 3 pads */
+
+/* set: set m's R x cols columns read in place at set + m * set_stride elements (set_stride >= cols R;
+ * no alignment beyond the element's; never written). 1 <= R = set_rows <= NMH_PLAYER_MAX_ROWS (entity)
+ * or NMH_ITEM_MAX_ROWS (item). Outputs, any of which may be NULL, not all:
+ *   idx uint8 [n_sets, R, D] and cont float32 [n_sets, R, C]: every candidate's indices and x / s;
+ *   counts float32 [n_sets, D, 256]: the number of the set's candidates with idx_d == i (exact);
+ *   sums float32 [n_sets, C]: the float32 sum of the raw column, not divided, in one fixed order;
+ *   mine_idx int32 [n_sets], mine_i uint8 [n_sets, D], mine_c float32 [n_sets, C] (entity kind only):
+ *     the smallest j < R with col 0 == id and col 0 != 0, else 0, and that candidate's idx and cont;
+ *     ids, id_stride, id_kind as in nmh_player_features, and ids may be NULL only if all three are.
+ * n_sets == 0 is a no-op. */
+NMH_API int nmh_embed_features(int32_t kind, int32_t n_sets, const void* set, int64_t set_stride, int32_t elem_kind,
+                               int32_t set_rows, const void* ids, int64_t id_stride, int32_t id_kind, uint8_t* idx,
+                               float* cont, float* counts, float* sums, int32_t* mine_idx, uint8_t* mine_i,
+                               float* mine_c, void* stream);
+
+/* Obs row r reads set r / share (share >= 1). pq [n_rows, n_heads, Q], 16-byte aligned, Q the kind's
+ * *_QUERY: pq[256 d + i] scores index i of discrete column d, pq[256 D + c] weighs continuous column
+ * c, pq[256 D + C] is the bias, the rest pads. out [n_rows, out_stride]; mask as in nmh_forward; both
+ * strides cover the furthest head's set_rows + 1 entries.
+ * out[r][out_off[h] + j], j < R legal: v = pq[256 D + C]; v += pq[256 d + idx_d], d ascending;
+ * v = fmaf(x_c / s_c, pq[256 D + c], v), c ascending. Illegal j and the no-op j = R: 0.0f. All R + 1
+ * entries are written, nothing else is, and a candidate that no head of the call allows is never
+ * read. n_rows == 0 is a no-op. */
+NMH_API int nmh_embed_logits(int32_t kind, const NmhSetHeads* sh, int32_t n_rows, const void* set,
+                             int64_t set_stride, int32_t elem_kind, int32_t set_rows, int32_t share,
+                             const void* mask, int64_t mask_stride, int32_t mask_kind, const float* pq, float* out,
+                             int64_t out_stride, void* stream);
+
+/* g_pq [n_rows, n_heads, Q]: over the head's legal j < R in ascending order, g_pq[256 d + i] = the
+ * sum of g_out[j] where idx_d(j) == i, g_pq[256 D + c] = fmaf(g_out[j], x_c / s_c, .), g_pq[256 D + C]
+ * = the sum of g_out[j]; the pads are written as 0. g_out [n_rows, g_stride] like out; its entries of
+ * illegal candidates and of the no-op are not read. No atomics: the same bits on every run. */
+NMH_API int nmh_embed_logits_backward(int32_t kind, const NmhSetHeads* sh, int32_t n_rows, const void* set,
+                                      int64_t set_stride, int32_t elem_kind, int32_t set_rows, int32_t share,
+                                      const void* mask, int64_t mask_stride, int32_t mask_kind, const float* g_out,
+                                      int64_t g_stride, float* g_pq, void* stream);
+
 /* ---- Decoder (SPEC.md §23): every action head of a row from the obs row itself, in one launch.
  * A head is dense (its logits are given) or a pointer head into one of up to NMH_MAX_SETS candidate
  * sets that are read in place; a pointer head's logits are §20's (item sets) or §21's (entity sets)

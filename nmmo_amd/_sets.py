@@ -1,7 +1,7 @@
-"""What `item.py` and `player.py` share: pointer heads over a candidate set that is read from the obs
-rows in place (include/nmmo_heads.h, NmhSetHeads; SPEC.md §20, §21). One C struct, one argument
-rule for the sets, one `torch.autograd.Function` over nmh_item_logits / nmh_player_logits and their
-backwards. A `SetSpec` holds what differs between the two kinds of set.
+"""What `item.py`, `player.py` and `embed.py` share: pointer heads over a candidate set that is read
+from the obs rows in place (include/nmmo_heads.h, NmhSetHeads; SPEC.md §20, §21, §25). One C struct,
+one argument rule for the sets, one `torch.autograd.Function` over nmh_item_logits / nmh_player_logits /
+nmh_embed_logits and their backwards. A `SetSpec` holds what differs between the kinds of set.
 """
 
 from __future__ import annotations
@@ -29,6 +29,7 @@ class SetSpec(NamedTuple):
     query: int  # floats per projected query
     max_rows: int
     share: bool  # whether several obs rows may read one set (the library's `share` argument)
+    kind: int | None = None  # the library call's leading `kind` argument (nmh_embed_*), if it has one
 
 
 class NmhSetHeads(ctypes.Structure):
@@ -58,7 +59,7 @@ def elem_kind(t: torch.Tensor, what: str) -> int:
 def set_arg(x: torch.Tensor, set_rows, spec: SetSpec):
     """(tensor kept alive, set stride in elements, R, NMH_ELEM_*) of candidate sets read in place:
     [M, R, cols], or [M, >= cols R] whose first cols R columns are the set."""
-    _, _, name, lead, noun, _, cols, _, max_rows, _ = spec
+    name, lead, noun, cols, max_rows = spec.name, spec.lead, spec.noun, spec.cols, spec.max_rows
     if x.dim() == 3:
         if x.shape[2] != cols:
             raise ValueError(f"{name} must be [{lead}, R, {cols}] or [{lead}, >= {cols} R], got {tuple(x.shape)}")
@@ -80,11 +81,12 @@ def set_arg(x: torch.Tensor, set_rows, spec: SetSpec):
 
 
 class SetLogits(torch.autograd.Function):
-    """`item_logits` and `player_logits`: the logits of up to four pointer heads over one set per row."""
+    """`item_logits`, `player_logits` and `embed_logits`: the logits of up to four pointer heads over
+    one set per row."""
 
     @staticmethod
     def forward(ctx, spec, sets, pq, mask_rows, mask_off, share, mask_kind, set_rows):
-        what, fn, name, _, _, one, _, query, _, shared = spec
+        what, fn, name, one, query, shared = spec.what, spec.fn, spec.name, spec.one, spec.query, spec.share
         if not (sets.is_cuda and pq.is_cuda and mask_rows.is_cuda):
             raise HeadsError(f"{what} runs on the GPU: {name}, pq and mask_rows must be device tensors")
         x, stride, rows, kind = set_arg(sets.detach(), set_rows, spec)
@@ -107,6 +109,8 @@ class SetLogits(torch.autograd.Function):
         out = torch.empty((n, n_heads * width), dtype=torch.float32, device=dev)
         # the set's arguments up to the mask: the library's entity entry points take no `share`
         head = (ctypes.byref(sh), n, x.data_ptr(), stride, kind, rows)
+        if spec.kind is not None:
+            head = (spec.kind,) + head
         if shared:
             head += (share,)
         with torch.cuda.device(dev):

@@ -70,6 +70,21 @@ class BaselineAgent(nn.Module):
                  fused_tile: bool = False, fused_tile_conv2: bool = False, fused_item: bool = False,
                  fused_player: bool = False, fused_decoder: bool = False, seed: int = 0, query_scale: float = 1.0):
         super().__init__()
+        self._calling(task_dim, fused_heads, fused_decoder, seed, query_scale)
+
+        self.tile_encoder = TileEncoder(hidden, fused=fused_tile, fused_conv2=fused_tile_conv2)
+        self.player_encoder = PlayerEncoder(hidden, hidden, fused=fused_player)
+        self.item_encoder = ItemEncoder(hidden, fused=fused_item)
+        self.inventory_encoder = _Fc(layout.INVENTORY_N_OBS * hidden, hidden)
+        self.market_encoder = _Fc(hidden, hidden)
+        self.task_encoder = _Fc(task_dim, hidden)
+        self.proj_fc = nn.Linear(6 * hidden, hidden)
+        self.action_decoder = ActionDecoder(hidden, self.dims)
+        self.value_head = nn.Linear(hidden, 1)
+
+    def _calling(self, task_dim: int, fused_heads: bool, fused_decoder: bool, seed: int, query_scale: float):
+        """What `decode_actions` and `masked` need besides the modules: the sampling state and where the
+        sections, masks and heads lie in an obs row. (`reduced.ReducedAgent` shares it.)"""
         self.fused_heads, self.fused_decoder = bool(fused_heads), bool(fused_decoder)
         self.seed = int(seed)
         self.draws = 0  # sampling calls so far: the `offset` of the next one
@@ -85,16 +100,6 @@ class BaselineAgent(nn.Module):
             assert s is None or self.dims[k] == self.sections[s][1] + 1, (k, s)
         self.pointer = [k for k, s in enumerate(self.head_set) if s >= 0]  # in head order: pq's slots
         self.set_heads = [[k for k in self.pointer if self.head_set[k] == s] for s in range(len(SETS))]
-
-        self.tile_encoder = TileEncoder(hidden, fused=fused_tile, fused_conv2=fused_tile_conv2)
-        self.player_encoder = PlayerEncoder(hidden, hidden, fused=fused_player)
-        self.item_encoder = ItemEncoder(hidden, fused=fused_item)
-        self.inventory_encoder = _Fc(layout.INVENTORY_N_OBS * hidden, hidden)
-        self.market_encoder = _Fc(hidden, hidden)
-        self.task_encoder = _Fc(task_dim, hidden)
-        self.proj_fc = nn.Linear(6 * hidden, hidden)
-        self.action_decoder = ActionDecoder(hidden, self.dims)
-        self.value_head = nn.Linear(hidden, 1)
 
     # ---------------------------------------------------------------- views of the obs rows
     def section(self, obs: torch.Tensor, name: str) -> torch.Tensor:
@@ -193,14 +198,7 @@ class BaselineAgent(nn.Module):
             width = self.sections[name][1] + 1
             enc = self.player_encoder if name == "Entity" else self.item_encoder
             if enc.fused:
-                from .item import QUERY as ITEM_QUERY, item_logits
-                from .player import QUERY as PLAYER_QUERY, player_logits
-
-                if ks[0] not in slots:
-                    slots.update(self._fold(queries, name))
-                pq = torch.stack([slots[k][:, :PLAYER_QUERY if name == "Entity" else ITEM_QUERY] for k in ks], 1)
-                fn = player_logits if name == "Entity" else item_logits
-                lg = fn(self.section(obs, name), pq, obs, [self.mask_off[k] for k in ks], set_rows=width - 1)
+                lg = self._set_logits(name, ks, queries, obs, slots)
                 for i, k in enumerate(ks):
                     parts[k] = lg[:, i * width:(i + 1) * width]
             else:
@@ -209,6 +207,18 @@ class BaselineAgent(nn.Module):
                 for k in ks:
                     parts[k] = torch.matmul(padded, queries[k].unsqueeze(-1)).squeeze(-1)
         return torch.cat(parts, 1)
+
+    def _set_logits(self, name: str, ks, queries, obs: torch.Tensor, slots: dict) -> torch.Tensor:
+        """[N, len(ks) * (R + 1)]: the heads `ks` over set `name` from its fused encoder's kernel. `slots`
+        keeps the folded queries between the two item sets of one `logits` call."""
+        from .item import QUERY as ITEM_QUERY, item_logits
+        from .player import QUERY as PLAYER_QUERY, player_logits
+
+        if ks[0] not in slots:
+            slots.update(self._fold(queries, name))
+        pq = torch.stack([slots[k][:, :PLAYER_QUERY if name == "Entity" else ITEM_QUERY] for k in ks], 1)
+        fn = player_logits if name == "Entity" else item_logits
+        return fn(self.section(obs, name), pq, obs, [self.mask_off[k] for k in ks], set_rows=self.sections[name][1])
 
     def masked(self, logits: torch.Tensor, obs: torch.Tensor, action: torch.Tensor | None = None,
                greedy: bool = False):
@@ -268,11 +278,13 @@ class RecurrentBaselineAgent(nn.Module):
     each [num_layers, B, hidden], or None for zeros. Under `torch.no_grad()` with `fused_lstm` a given
     state is updated in place and returned."""
 
+    POLICY = BaselineAgent  # what `policy` is: `reduced.RecurrentReducedAgent` names another
+
     def __init__(self, task_dim: int = 2048, hidden: int = 256, num_layers: int = 1, fused_lstm: bool = False,
                  **baseline_flags):
         super().__init__()
         self.fused_lstm = bool(fused_lstm)
-        self.policy = BaselineAgent(task_dim, hidden, **baseline_flags)
+        self.policy = self.POLICY(task_dim, hidden=hidden, **baseline_flags)
         if self.fused_lstm:
             from .lstm import LSTM
 

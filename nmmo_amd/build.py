@@ -36,7 +36,8 @@ LIBS = {
                 "native_obs.hip", "flat_obs.hip", "p2p.hip", "capi.hip"],
                ["agent_obs.h", "common.h", "host_api.h", "kernels.h", "obs_layout.h", "wire.h"], ["nmmo_hip.h"],
                ["-ldl"]),
-    "heads": Lib("libnmmo_heads.so", ["heads.hip", "tile_enc.hip", "item_enc.hip", "player_enc.hip", "decoder.hip"],
+    "heads": Lib("libnmmo_heads.so", ["heads.hip", "tile_enc.hip", "item_enc.hip", "player_enc.hip", "embed_enc.hip",
+                  "decoder.hip"],
                  ["common.h", "host_api.h", "heads_dev.h", "heads_host.h", "item_dev.h", "player_dev.h"],
                  ["nmmo_hip.h", "nmmo_heads.h"]),
     "ppo": Lib("libnmmo_ppo.so", ["ppo.hip"], ["host_api.h"], ["nmmo_ppo.h"]),

@@ -1,7 +1,7 @@
 // heads_host.h — the host code that the translation units of libnmmo_heads.so share (heads.hip,
-// tile_enc.hip, item_enc.hip, player_enc.hip, decoder.hip): the library's one error text, the
+// tile_enc.hip, item_enc.hip, player_enc.hip, embed_enc.hip, decoder.hip): the library's one error text, the
 // launch-error and alignment helpers, the argument rules of "heads over a candidate set"
-// (nmh_item_logits / nmh_player_logits and their backwards) and the head plan of the calls that mix
+// (nmh_item_logits / nmh_player_logits / nmh_embed_logits and their backwards) and the head plan of the calls that mix
 // dense and pointer heads (nmh_pointer_*, nmh_decoder_*). Host only; no kernel depends on it.
 #pragma once
 

@@ -35,7 +35,7 @@
 #include "common.h"
 #include "heads_dev.h"   // wave_sync, legal_at
 #include "heads_host.h"  // heads_fail, heads_launched, aligned16, check_set, check_logits, HEADS_SET_LAUNCH
-#include "player_dev.h"  // stage_rows, player_logit, feature_col, npc_class: shared with decoder.hip
+#include "player_dev.h"  // legal_list_heads, stage_rows, player_logit, feature_col, npc_class
 #include "../../include/nmmo_heads.h"
 
 using namespace nmmo;
@@ -150,34 +150,6 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void nmh_player_own_kernel(
 }
 
 // ---------------------------------------------------------------- pointer logits
-// The j < R that any head allows, ascending, into list[0, cnt) as j | heads << 12; returns cnt
-// (wave-uniform). ZERO: orow[out_off[h] + j] = 0 for every j < R head h forbids.
-template <int MK, bool ZERO>
-__device__ __forceinline__ int player_legal_list(const NmhPlayerHeads& ph, const void* __restrict__ mask, int64_t mbase,
-                                                 int R, uint16_t* list, float* __restrict__ orow) {
-  const int H = ph.n_heads, lane = lane_id();
-  int cnt = 0;
-  for (int b0 = 0; b0 < R; b0 += 64) {  // (wave-uniform trip count: every lane ballots)
-    const int j = b0 + lane;
-    bool lg[kMaxHeads];
-#pragma unroll
-    for (int h = 0; h < kMaxHeads; ++h)  // unconditional loads, all in flight
-      lg[h] = h < H && legal_at<MK>(mask, mbase + ph.mask_off[h] + min(j, R - 1));
-    unsigned hm = 0;
-#pragma unroll
-    for (int h = 0; h < kMaxHeads; ++h) {
-      if (h < H && j < R) {
-        if (lg[h]) hm |= 1u << h;
-        else if (ZERO) orow[ph.out_off[h] + j] = 0.0f;
-      }
-    }
-    const uint64_t b = __ballot(hm != 0);
-    if (hm) list[cnt + __popcll(b & lanes_below())] = (uint16_t)(j | (hm << kHeadShift));
-    cnt += __popcll(b);
-  }
-  return cnt;
-}
-
 template <typename T, int MK>
 __global__ __launch_bounds__(64 * kRowsPerBlock) void nmh_player_logits_kernel(
     NmhPlayerHeads ph, int n_rows, const T* __restrict__ ents, int64_t ent_stride, int R,
@@ -195,7 +167,7 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void nmh_player_logits_kernel(
   for (int i = lane; i < H * kQ; i += 64) spq[i] = pq[r * H * kQ + i];
   const T* __restrict__ set = ents + r * ent_stride;
   float* __restrict__ orow = out + r * os;
-  const int cnt = player_legal_list<MK, true>(ph, mask, r * ms, R, list, orow);
+  const int cnt = legal_list_heads<MK, true>(ph, mask, r * ms, R, list, orow);
 #pragma unroll
   for (int h = 0; h < kMaxHeads; ++h)
     if (h < H && lane == h) orow[ph.out_off[h] + R] = 0.0f;  // the no-op entries
@@ -230,7 +202,7 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void nmh_player_logits_backward
   uint16_t* list = s_list[w];
   const T* __restrict__ set = ents + r * ent_stride;
   const float* __restrict__ grow = g_out + r * gs;
-  const int cnt = player_legal_list<MK, false>(ph, mask, r * ms, R, list, nullptr);
+  const int cnt = legal_list_heads<MK, false>(ph, mask, r * ms, R, list, nullptr);
   // the column feature f reads; the constant (f = 35) and the lanes beyond read column 0 and drop it
   const int col = f < kF ? feature_col(f) : 0;
   float acc[kMaxHeads] = {};

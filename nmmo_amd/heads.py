@@ -27,7 +27,8 @@ SYMBOLS = ["nmh_forward", "nmh_backward", "nmh_pointer_forward", "nmh_pointer_ba
            "nmh_tile_backward", "nmh_tile2_forward", "nmh_tile2_backward", "nmh_item_features", "nmh_item_logits",
            "nmh_item_logits_backward", "nmh_player_features", "nmh_player_logits", "nmh_player_logits_backward",
            "nmh_decoder_forward", "nmh_decoder_backward", "nmh_forward_argmax", "nmh_pointer_forward_argmax",
-           "nmh_decoder_forward_argmax", "nmh_last_error", "nmh_build_info"]
+           "nmh_decoder_forward_argmax", "nmh_embed_features", "nmh_embed_logits", "nmh_embed_logits_backward",
+           "nmh_last_error", "nmh_build_info"]
 MAX_HEADS, MAX_DIM = 16, 2048
 MAX_SETS, MAX_KEY_DIM = 4, 256
 MASK_F32, MASK_U8 = 0, 1
@@ -67,6 +68,10 @@ def declare(L):
     L.nmh_player_features.argtypes = [i32, vp, i64, i32, i32, vp, i64, i32, vp, vp, vp, vp, vp]  # nmmo_amd/player.py
     L.nmh_player_logits.argtypes = [vp, i32, vp, i64, i32, i32, vp, i64, i32, vp, vp, i64, vp]
     L.nmh_player_logits_backward.argtypes = [vp, i32, vp, i64, i32, i32, vp, i64, i32, vp, i64, vp, vp]
+    # nmmo_amd/embed.py: the kind first, then the set arguments of the item calls
+    L.nmh_embed_features.argtypes = [i32, i32, vp, i64, i32, i32, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.nmh_embed_logits.argtypes = [i32] + L.nmh_item_logits.argtypes
+    L.nmh_embed_logits_backward.argtypes = [i32] + L.nmh_item_logits_backward.argtypes
     L.nmh_decoder_forward.argtypes = [hp, vp, i32, vp, vp, i64, vp, i64, i32, vp, u64, u64, ctypes.c_uint32,
                                       vp, vp, vp, vp, vp, vp]  # nmmo_amd/decoder.py
     L.nmh_decoder_backward.argtypes = [hp, vp, i32, vp, vp, i64, vp, i64, i32, vp, vp, vp, vp, vp, vp, i64, vp, vp]
