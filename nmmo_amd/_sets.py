@@ -1,7 +1,8 @@
 """What `item.py`, `player.py` and `embed.py` share: pointer heads over a candidate set that is read
 from the obs rows in place (include/nmmo_heads.h, NmhSetHeads; SPEC.md §20, §21, §25). One C struct,
 one argument rule for the sets, one `torch.autograd.Function` over nmh_item_logits / nmh_player_logits /
-nmh_embed_logits and their backwards. A `SetSpec` holds what differs between the kinds of set.
+nmh_embed_logits and their backwards, and the encoders' set reshaping, id argument and own-row rule.
+A `SetSpec` holds what differs between the kinds of set.
 """
 
 from __future__ import annotations
@@ -78,6 +79,40 @@ def set_arg(x: torch.Tensor, set_rows, spec: SetSpec):
     kind = elem_kind(x, name)
     x, stride = heads.rows_arg(x, rows * cols)
     return x, stride, rows, kind
+
+
+def set_rows_of(x: torch.Tensor, set_rows, cols: int) -> int:
+    """R of sets [M, R, cols] or [M, >= cols R]: by default all whole candidates of the width."""
+    return x.shape[1] if x.dim() == 3 else (x.shape[1] // cols if set_rows is None else int(set_rows))
+
+
+def as_sets(x: torch.Tensor, set_rows, cols: int) -> torch.Tensor:
+    """[M, R, cols] of sets [M, R, cols] or [M, >= cols R], for the plain-torch paths."""
+    if x.dim() == 3:
+        return x
+    rows = set_rows_of(x, set_rows, cols)
+    return x[:, :rows * cols].reshape(x.shape[0], rows, cols)
+
+
+def id_arg(ids: torch.Tensor, n: int):
+    """(tensor kept alive, element stride, NMH_ELEM_*) of the rows' AgentId read in place: [N] or
+    [N, 1], any positive stride (a column of the obs rows)."""
+    if ids.dim() == 2 and ids.shape[1] == 1:
+        ids = ids[:, 0]
+    if ids.dim() != 1 or ids.shape[0] != n:
+        raise ValueError(f"ids must be [{n}] or [{n}, 1], got {tuple(ids.shape)}")
+    kind = elem_kind(ids, "ids")
+    if n > 1 and ids.stride(0) < 1:
+        ids = ids.contiguous()
+    return ids, max(ids.stride(0), 1), kind
+
+
+def own_row_index(col: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
+    """The index [N] int64 of each row's own entity from the entities' id column [N, R] (floating) and
+    the rows' AgentId: the first j whose id equals the row's and is not 0, else 0 (SPEC §21's rule). A
+    NaN id matches nothing."""
+    match = (col == ids.reshape(-1, 1).to(col.dtype)) & (col != 0)
+    return torch.where(match.any(1), match.int().argmax(1), torch.zeros_like(match.sum(1)))
 
 
 class SetLogits(torch.autograd.Function):

@@ -38,7 +38,7 @@ LIBS = {
                ["-ldl"]),
     "heads": Lib("libnmmo_heads.so", ["heads.hip", "tile_enc.hip", "item_enc.hip", "player_enc.hip", "embed_enc.hip",
                   "decoder.hip"],
-                 ["common.h", "host_api.h", "heads_dev.h", "heads_host.h", "item_dev.h", "player_dev.h"],
+                 ["common.h", "host_api.h", "heads_dev.h", "heads_host.h", "item_dev.h", "player_dev.h", "set_dev.h"],
                  ["nmmo_hip.h", "nmmo_heads.h"]),
     "ppo": Lib("libnmmo_ppo.so", ["ppo.hip"], ["host_api.h"], ["nmmo_ppo.h"]),
     "lstm": Lib("libnmmo_lstm.so", ["lstm.hip"], ["host_api.h"], ["nmmo_lstm.h"]),

@@ -20,7 +20,7 @@
 // Forward, per pointer head: legal_list (heads_dev.h) fills the head's tile entries with -inf and
 // lists the legal candidates; an item head then takes one listed candidate per lane (load_item,
 // item_logit: item_dev.h), an entity head stages 64 listed candidates' rows and takes one per lane
-// (stage_rows, player_logit: player_dev.h). Candidates no head allows are never addressed.
+// (stage_rows: set_dev.h; player_logit: player_dev.h). Candidates no head allows are never addressed.
 // Backward, per pointer head: the same list; g_j = nmh_backward_kernel's expression on the recomputed
 // logit, kept in LDS by list position; then lane f owns feature f of the head's query and walks the
 // list in ascending order with one fmaf per candidate. No atomics: the same bits on every run.
@@ -34,6 +34,7 @@
 #include "heads_host.h"  // heads_fail, heads_launched, aligned16, check_head_plan
 #include "item_dev.h"
 #include "player_dev.h"
+#include "set_dev.h"
 #include "../../include/nmmo_heads.h"
 
 using namespace nmmo;
@@ -47,7 +48,7 @@ constexpr int kSlot = NMH_DECODER_QUERY;
 constexpr int kRowsBytes = kChunk * player_dev::kC * 4;
 
 static_assert(kSlot >= NMH_PLAYER_QUERY && kSlot >= NMH_ITEM_QUERY && kSlot <= 64, "a lane per float of a slot");
-static_assert(NMH_ITEM_MAX_ROWS < (1 << player_dev::kHeadShift), "stage_rows masks a list entry to 12 bits");
+static_assert(NMH_ITEM_MAX_ROWS < (1 << set_dev::kHeadShift), "stage_rows masks a list entry to 12 bits");
 static_assert(2 * (NMH_MAX_DIM * 4 + NMH_MAX_HEADS * kSlot * 4 + NMH_PLAYER_MAX_ROWS * 2 + kRowsBytes) <= kMaxLds &&
                   2 * (NMH_MAX_DIM * 4 + NMH_MAX_HEADS * kSlot * 4 + NMH_ITEM_MAX_ROWS * 2) <= kMaxLds,
               "two waves of any accepted shape fit 64 KiB");
@@ -127,7 +128,7 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void nmh_decoder_forward_kernel
     } else {
       for (int i0 = 0; i0 < cnt; i0 += kChunk) {
         const int c = min(kChunk, cnt - i0);
-        player_dev::stage_rows(cand, m.list, i0, c, m.rows);
+        set_dev::stage_rows<player_dev::kC, player_dev::kC>(cand, m.list, i0, c, m.rows);
         wave_sync();
         if (lane < c) s[off + m.list[i0 + lane]] = player_dev::player_logit(q, m.rows + lane * player_dev::kC);
         wave_sync();  // the next chunk overwrites the rows
@@ -214,7 +215,7 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void nmh_decoder_backward_kerne
       const int col = f < player_dev::kF ? player_dev::feature_col(f) : 0;
       for (int i0 = 0; i0 < cnt; i0 += kChunk) {
         const int c = min(kChunk, cnt - i0);
-        player_dev::stage_rows(cand, m.list, i0, c, m.rows);
+        set_dev::stage_rows<player_dev::kC, player_dev::kC>(cand, m.list, i0, c, m.rows);
         wave_sync();
         if (f < c) sg[f] = grad(m.list[i0 + f], player_dev::player_logit(q, m.rows + f * player_dev::kC));
         wave_sync();

@@ -28,19 +28,19 @@
 
 #include "common.h"
 #include "heads_dev.h"   // wave_sync
-#include "heads_host.h"  // heads_fail, heads_launched, aligned16, check_set, check_logits, HEADS_SET_LAUNCH
-#include "player_dev.h"  // legal_list_heads, kHeadShift
+#include "heads_host.h"  // heads_fail, heads_launched, check_set, check_ids, check_forward, check_backward, HEADS_SET_LAUNCH
+#include "set_dev.h"     // legal_list_heads, stage_rows, scan_set, load_id
 #include "../../include/nmmo_heads.h"
 
 using namespace nmmo;
-using nmmo::player_dev::kHeadShift;
-using nmmo::player_dev::legal_list_heads;
+using set_dev::kHeadShift;
+using set_dev::kJMask;
+using set_dev::legal_list_heads;
 
 namespace {
 
 constexpr int kBins = NMH_EMBED_BINS, kMaxHeads = NMH_ITEM_MAX_HEADS;
-constexpr int kThreads = 256, kRowsPerBlock = 4, kChunk = 64;
-constexpr int kJMask = (1 << kHeadShift) - 1;
+constexpr int kThreads = set_dev::kScanThreads, kRowsPerBlock = 4, kChunk = 64;
 
 // SPEC §25's two kinds. dslot / cslot: the discrete or continuous slot a column feeds, or -1.
 struct EntityKind {
@@ -89,16 +89,12 @@ static_assert(kind_is_sound<EntityKind>() && kind_is_sound<ItemKind>(), "SPEC §
 static_assert(EntityKind::cdiv(24) == 100.0f && EntityKind::cdiv(25) == 100.0f && EntityKind::cdiv(26) == 10.0f &&
                   EntityKind::cdiv(11) == 10.0f && EntityKind::cdiv(10) == 100.0f && EntityKind::cdiv(2) == 100.0f,
               "the reference's divisors");
-static_assert(kMaxHeads <= 16 - kHeadShift && kBins == 256, "a list entry is 16 bits, an index a byte");
+static_assert(kBins == 256, "an index is a byte");
 
 // SPEC §25's index rule: clip(trunc(x + off), 0, 255), NaN -> 0
 __device__ inline int embed_idx(float x, float off) {
   const float v = x + off;
   return v >= 0.0f ? (v >= (float)(kBins - 1) ? kBins - 1 : (int)v) : 0;
-}
-
-__device__ inline float load_id(const void* __restrict__ ids, int64_t i, int id_kind) {
-  return id_kind == NMH_ELEM_F32 ? static_cast<const float*>(ids)[i] : (float)static_cast<const int16_t*>(ids)[i];
 }
 
 // ---------------------------------------------------------------- features, counts, sums, own row
@@ -115,7 +111,7 @@ __global__ __launch_bounds__(kThreads) void nmh_embed_features_kernel(
     const T* __restrict__ sets, int64_t set_stride, int R, const void* __restrict__ ids, int64_t id_stride, int id_kind,
     uint8_t* __restrict__ idx, float* __restrict__ cont, float* __restrict__ counts, float* __restrict__ sums,
     int32_t* __restrict__ mine_idx, uint8_t* __restrict__ mine_i, float* __restrict__ mine_c) {
-  constexpr int kCols = K::kCols, kD = K::kD, kC = K::kC, kSlots = kThreads / kCols, kU = 4;
+  constexpr int kCols = K::kCols, kD = K::kD, kC = K::kC, kSlots = kThreads / kCols;
   __shared__ float s_part[kSlots][kCols];
   __shared__ int s_cnt[kD * kBins];
   __shared__ int s_first;
@@ -126,32 +122,14 @@ __global__ __launch_bounds__(kThreads) void nmh_embed_features_kernel(
   if (tid == 0) s_first = R;
   __syncthreads();
   const T* __restrict__ set = sets + m * set_stride;
-  const float id = own ? load_id(ids, m * id_stride, id_kind) : 0.0f;
+  const float id = own ? set_dev::load_id(ids, m * id_stride, id_kind) : 0.0f;
   const int d = K::dslot(c);
-  if (slot < kSlots && (all || c == 0)) {
-    float acc = 0.0f;
-    for (int j0 = 0; j0 < R; j0 += kSlots * kU) {
-      T v[kU];
-#pragma unroll
-      for (int u = 0; u < kU; ++u) {
-        const int j = j0 + u * kSlots + slot;
-        v[u] = j < R ? set[(int64_t)j * kCols + c] : (T)0;
-      }
-#pragma unroll
-      for (int u = 0; u < kU; ++u) {
-        const int j = j0 + u * kSlots + slot;
-        if (j < R) {
-          const float x = (float)v[u];
-          acc += x;
-          if (d >= 0 && counts) atomicAdd(&s_cnt[d * kBins + embed_idx(x, K::doff(d))], 1);
-          if (c == 0 && own && x == id && x != 0.0f) atomicMin(&s_first, j);
-          const int64_t e = m * R + j;
-          put_feature<K>(idx ? idx + e * kD : nullptr, cont ? cont + e * kC : nullptr, c, x);
-        }
-      }
-    }
-    s_part[slot][c] = acc;
-  }
+  if (slot < kSlots && (all || c == 0))
+    s_part[slot][c] = set_dev::scan_set<kCols>(set, R, slot, c, own, id, &s_first, [&](int j, float x) {
+      if (d >= 0 && counts) atomicAdd(&s_cnt[d * kBins + embed_idx(x, K::doff(d))], 1);
+      const int64_t e = m * R + j;
+      put_feature<K>(idx ? idx + e * kD : nullptr, cont ? cont + e * kC : nullptr, c, x);
+    });
   __syncthreads();
   if (sums && tid < kC) {
     const int col = K::ccol(tid);
@@ -171,35 +149,6 @@ __global__ __launch_bounds__(kThreads) void nmh_embed_features_kernel(
 }
 
 // ---------------------------------------------------------------- pointer logits
-// The columns of listed candidates [i0, i0 + n) into rows[n][cols | 1] as float32: lane e takes
-// element e % cols of candidate e / cols, so a candidate's elements are consecutive lanes' loads.
-template <typename K, typename T>
-__device__ __forceinline__ void stage_set_rows(const T* __restrict__ set, const uint16_t* list, int i0, int n,
-                                               float* rows) {
-  constexpr int kU = 4, kCols = K::kCols, kS = kCols | 1;
-  const int tot = n * kCols;
-  for (int e0 = lane_id(); e0 < tot; e0 += 64 * kU) {
-    T v[kU];
-#pragma unroll
-    for (int u = 0; u < kU; ++u) {
-      const int e = e0 + 64 * u;
-      v[u] = (T)0;
-      if (e < tot) {
-        const int k = e / kCols;
-        v[u] = set[(int64_t)(list[i0 + k] & kJMask) * kCols + (e - k * kCols)];
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < kU; ++u) {
-      const int e = e0 + 64 * u;
-      if (e < tot) {
-        const int k = e / kCols;
-        rows[k * kS + (e - k * kCols)] = (float)v[u];
-      }
-    }
-  }
-}
-
 template <typename K, typename T, int MK>
 __device__ __forceinline__ void embed_logits_body(const NmhSetHeads& sh, int n_rows, const T* __restrict__ sets,
                                                   int64_t set_stride, int R, int share, const void* __restrict__ mask,
@@ -230,7 +179,7 @@ __device__ __forceinline__ void embed_logits_body(const NmhSetHeads& sh, int n_r
   wave_sync();
   for (int i0 = 0; i0 < cnt; i0 += kChunk) {
     const int n = min(kChunk, cnt - i0);
-    stage_set_rows<K>(set, list, i0, n, rows);
+    set_dev::stage_rows<K::kCols, kS>(set, list, i0, n, rows);
     wave_sync();
     if (lane < n) {
       const int entry = list[i0 + lane], j = entry & kJMask, hm = entry >> kHeadShift;
@@ -285,7 +234,7 @@ __device__ __forceinline__ void embed_backward_body(const NmhSetHeads& sh, int n
   wave_sync();
   for (int i0 = 0; i0 < cnt; i0 += kChunk) {
     const int n = min(kChunk, cnt - i0);
-    stage_set_rows<K>(set, list, i0, n, rows);
+    set_dev::stage_rows<K::kCols, kS>(set, list, i0, n, rows);
     if (f < n) {  // lane k: listed candidate k's g_out in the heads that allow it, no other entry
       const int entry = list[i0 + f], j = entry & kJMask, hm = entry >> kHeadShift;
 #pragma unroll
@@ -388,10 +337,8 @@ int nmh_embed_features(int32_t kind, int32_t n_sets, const void* set, int64_t se
   if (own) {
     if (kind != NMH_EMBED_ENTITY)
       return heads_fail(NMH_E_INVALID, "%s: mine_idx, mine_i and mine_c are the entity kind's", fn);
-    if (!ids) return heads_fail(NMH_E_INVALID, "%s: ids is NULL but a mine output is not", fn);
-    if (id_kind != NMH_ELEM_F32 && id_kind != NMH_ELEM_I16)
-      return heads_fail(NMH_E_INVALID, "%s: unknown id_kind %d", fn, id_kind);
-    if (id_stride < 1) return heads_fail(NMH_E_INVALID, "%s: id_stride %lld < 1", fn, (long long)id_stride);
+    rc = check_ids(fn, ids, id_stride, id_kind, "a mine output is");
+    if (rc != NMH_OK) return rc;
   }
   if (n_sets == 0) return NMH_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -415,12 +362,9 @@ int nmh_embed_logits(int32_t kind, const NmhSetHeads* sh, int32_t n_rows, const 
   const char* fn = "nmh_embed_logits";
   int rc = check_kind(fn, kind);
   if (rc != NMH_OK) return rc;
-  rc = check_logits(fn, kEmbedSets[kind], sh, n_rows, set, set_stride, elem_kind, set_rows, share, mask, mask_stride,
-                    mask_kind, "out", out, "out_stride", out_stride);
-  if (rc != NMH_OK) return rc;
-  if (!pq) return heads_fail(NMH_E_INVALID, "%s: pq is NULL", fn);
-  if (!aligned16(pq)) return heads_fail(NMH_E_INVALID, "%s: pq is not 16-byte aligned", fn);
-  if (n_rows == 0) return NMH_OK;
+  rc = check_forward(fn, kEmbedSets[kind], sh, n_rows, set, set_stride, elem_kind, set_rows, share, mask, mask_stride,
+                     mask_kind, pq, out, out_stride);
+  if (rc != NMH_OK || n_rows == 0) return rc;
   if (kind == NMH_EMBED_ENTITY)
     HEADS_SET_LAUNCH(nmh_embed_entity_logits_kernel, elem_kind, mask_kind, kRowsPerBlock, stream, sh, n_rows, set,
                      set_stride, set_rows, share, mask, mask_stride, pq, out, out_stride);
@@ -437,11 +381,9 @@ int nmh_embed_logits_backward(int32_t kind, const NmhSetHeads* sh, int32_t n_row
   const char* fn = "nmh_embed_logits_backward";
   int rc = check_kind(fn, kind);
   if (rc != NMH_OK) return rc;
-  rc = check_logits(fn, kEmbedSets[kind], sh, n_rows, set, set_stride, elem_kind, set_rows, share, mask, mask_stride,
-                    mask_kind, "g_out", g_out, "g_stride", g_stride);
-  if (rc != NMH_OK) return rc;
-  if (!g_pq) return heads_fail(NMH_E_INVALID, "%s: g_pq is NULL", fn);
-  if (n_rows == 0) return NMH_OK;
+  rc = check_backward(fn, kEmbedSets[kind], sh, n_rows, set, set_stride, elem_kind, set_rows, share, mask, mask_stride,
+                      mask_kind, g_out, g_stride, g_pq);
+  if (rc != NMH_OK || n_rows == 0) return rc;
   if (kind == NMH_EMBED_ENTITY)
     HEADS_SET_LAUNCH(nmh_embed_entity_logits_backward_kernel, elem_kind, mask_kind, kRowsPerBlock, stream, sh, n_rows,
                      set, set_stride, set_rows, share, mask, mask_stride, g_out, g_stride, g_pq);

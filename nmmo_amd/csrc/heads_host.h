@@ -45,6 +45,15 @@ inline int check_set(const char* fn, const SetKind& k, const void* set, int64_t 
   return NMH_OK;
 }
 
+// the rows' ids of a features call that asks for the own row; `mine` names the outputs that need them
+inline int check_ids(const char* fn, const void* ids, int64_t id_stride, int32_t id_kind, const char* mine) {
+  if (!ids) return heads_fail(NMH_E_INVALID, "%s: ids is NULL but %s not", fn, mine);
+  if (id_kind != NMH_ELEM_F32 && id_kind != NMH_ELEM_I16)
+    return heads_fail(NMH_E_INVALID, "%s: unknown id_kind %d", fn, id_kind);
+  if (id_stride < 1) return heads_fail(NMH_E_INVALID, "%s: id_stride %lld < 1", fn, (long long)id_stride);
+  return NMH_OK;
+}
+
 // the rules a *_logits entry point and its backward share; `out` names the [n_rows, out_stride]
 // argument. Entity sets are not shared between rows: their entry points pass share = 1.
 inline int check_logits(const char* fn, const SetKind& k, const NmhSetHeads* sh, int32_t n_rows, const void* set,
@@ -73,6 +82,31 @@ inline int check_logits(const char* fn, const SetKind& k, const NmhSetHeads* sh,
       return heads_fail(NMH_E_INVALID, "%s: %s %lld < out_off[%d] + set_rows + 1 = %lld", fn, stride_name,
                         (long long)out_stride, h, (long long)sh->out_off[h] + set_rows + 1);
   }
+  return NMH_OK;
+}
+
+// every rule of a *_logits entry point: check_logits on out / out_stride, then the projected queries
+inline int check_forward(const char* fn, const SetKind& k, const NmhSetHeads* sh, int32_t n_rows, const void* set,
+                         int64_t stride, int32_t elem_kind, int32_t set_rows, int32_t share, const void* mask,
+                         int64_t mask_stride, int32_t mask_kind, const float* pq, const float* out,
+                         int64_t out_stride) {
+  const int rc = check_logits(fn, k, sh, n_rows, set, stride, elem_kind, set_rows, share, mask, mask_stride, mask_kind,
+                              "out", out, "out_stride", out_stride);
+  if (rc != NMH_OK) return rc;
+  if (!pq) return heads_fail(NMH_E_INVALID, "%s: pq is NULL", fn);
+  if (!aligned16(pq)) return heads_fail(NMH_E_INVALID, "%s: pq is not 16-byte aligned", fn);
+  return NMH_OK;
+}
+
+// every rule of a *_logits_backward entry point: check_logits on g_out / g_stride, then g_pq
+inline int check_backward(const char* fn, const SetKind& k, const NmhSetHeads* sh, int32_t n_rows, const void* set,
+                          int64_t stride, int32_t elem_kind, int32_t set_rows, int32_t share, const void* mask,
+                          int64_t mask_stride, int32_t mask_kind, const float* g_out, int64_t g_stride,
+                          const float* g_pq) {
+  const int rc = check_logits(fn, k, sh, n_rows, set, stride, elem_kind, set_rows, share, mask, mask_stride, mask_kind,
+                              "g_out", g_out, "g_stride", g_stride);
+  if (rc != NMH_OK) return rc;
+  if (!g_pq) return heads_fail(NMH_E_INVALID, "%s: g_pq is NULL", fn);
   return NMH_OK;
 }
 

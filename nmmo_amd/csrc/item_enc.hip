@@ -29,7 +29,7 @@
 
 #include "common.h"
 #include "heads_dev.h"   // wave_sync, legal_at
-#include "heads_host.h"  // heads_fail, heads_launched, aligned16, check_set, check_logits, HEADS_SET_LAUNCH
+#include "heads_host.h"  // heads_fail, heads_launched, check_set, check_forward, check_backward, HEADS_SET_LAUNCH
 #include "item_dev.h"    // load_item, item_logit, item_feature, item_class: shared with decoder.hip
 #include "../../include/nmmo_heads.h"
 
@@ -265,12 +265,9 @@ int nmh_item_logits(const NmhItemHeads* ih, int32_t n_rows, const void* items, i
                     int32_t set_rows, int32_t share, const void* mask, int64_t mask_stride, int32_t mask_kind,
                     const float* pq, float* out, int64_t out_stride, void* stream) {
   const char* fn = "nmh_item_logits";
-  const int rc = check_logits(fn, kItemSets, ih, n_rows, items, item_stride, item_kind, set_rows, share, mask,
-                              mask_stride, mask_kind, "out", out, "out_stride", out_stride);
-  if (rc != NMH_OK) return rc;
-  if (!pq) return heads_fail(NMH_E_INVALID, "%s: pq is NULL", fn);
-  if (!aligned16(pq)) return heads_fail(NMH_E_INVALID, "%s: pq is not 16-byte aligned", fn);
-  if (n_rows == 0) return NMH_OK;
+  const int rc = check_forward(fn, kItemSets, ih, n_rows, items, item_stride, item_kind, set_rows, share, mask,
+                               mask_stride, mask_kind, pq, out, out_stride);
+  if (rc != NMH_OK || n_rows == 0) return rc;
   HEADS_SET_LAUNCH(nmh_item_logits_kernel, item_kind, mask_kind, kRowsPerBlock, stream, ih, n_rows, items, item_stride,
                    set_rows, share, mask, mask_stride, pq, out, out_stride);
   return heads_launched(fn);
@@ -281,11 +278,9 @@ int nmh_item_logits_backward(const NmhItemHeads* ih, int32_t n_rows, const void*
                              int64_t mask_stride, int32_t mask_kind, const float* g_out, int64_t g_stride,
                              float* g_pq, void* stream) {
   const char* fn = "nmh_item_logits_backward";
-  const int rc = check_logits(fn, kItemSets, ih, n_rows, items, item_stride, item_kind, set_rows, share, mask,
-                              mask_stride, mask_kind, "g_out", g_out, "g_stride", g_stride);
-  if (rc != NMH_OK) return rc;
-  if (!g_pq) return heads_fail(NMH_E_INVALID, "%s: g_pq is NULL", fn);
-  if (n_rows == 0) return NMH_OK;
+  const int rc = check_backward(fn, kItemSets, ih, n_rows, items, item_stride, item_kind, set_rows, share, mask,
+                                mask_stride, mask_kind, g_out, g_stride, g_pq);
+  if (rc != NMH_OK || n_rows == 0) return rc;
   HEADS_SET_LAUNCH(nmh_item_logits_backward_kernel, item_kind, mask_kind, kRowsPerBlock, stream, ih, n_rows, items,
                    item_stride, set_rows, share, mask, mask_stride, g_out, g_stride, g_pq);
   return heads_launched(fn);

@@ -33,21 +33,26 @@
 #include <stdint.h>
 
 #include "common.h"
-#include "heads_dev.h"   // wave_sync, legal_at
-#include "heads_host.h"  // heads_fail, heads_launched, aligned16, check_set, check_logits, HEADS_SET_LAUNCH
-#include "player_dev.h"  // legal_list_heads, stage_rows, player_logit, feature_col, npc_class
+#include "heads_dev.h"   // wave_sync
+#include "heads_host.h"  // heads_fail, heads_launched, check_set, check_ids, check_forward, check_backward, HEADS_SET_LAUNCH
+#include "player_dev.h"  // player_logit, feature_col, npc_class
+#include "set_dev.h"     // legal_list_heads, stage_rows, scan_set, load_id
 #include "../../include/nmmo_heads.h"
 
 using namespace nmmo;
 using namespace nmmo::player_dev;
+using set_dev::kHeadShift;
+using set_dev::kJMask;
+using set_dev::legal_list_heads;
+using set_dev::load_id;
 
 namespace {
 
 constexpr int kMaxRows = NMH_PLAYER_MAX_ROWS, kMaxHeads = NMH_PLAYER_MAX_HEADS;
-constexpr int kThreads = 256, kSlots = kThreads / kC, kRowsPerBlock = 4, kChunk = 64;
+constexpr int kThreads = set_dev::kScanThreads, kSlots = kThreads / kC, kRowsPerBlock = 4, kChunk = 64;
 
-static_assert(kC == 31 && kF == 35 && kTypes == 5 && kQ == 40 && kRaw == 29 && kSlots == 8, "the start-kit entity row");
-static_assert(kMaxRows <= (1 << kHeadShift) && kMaxHeads <= 16 - kHeadShift, "a list entry is 16 bits");
+static_assert(kSlots == 8, "eight entities a pass");
+static_assert(kMaxRows <= (1 << kHeadShift), "a list entry is 16 bits");
 
 // column c's part of x [35]: feature 0, the five one-hots, or feature c + 4
 __device__ inline void put_x(float* __restrict__ x, int c, float v) {
@@ -60,17 +65,12 @@ __device__ inline void put_x(float* __restrict__ x, int c, float v) {
   }
 }
 
-__device__ inline float load_id(const void* __restrict__ ids, int64_t i, int id_kind) {
-  return id_kind == NMH_PLAYER_F32 ? static_cast<const float*>(ids)[i] : (float)static_cast<const int16_t*>(ids)[i];
-}
-
 // ---------------------------------------------------------------- features, sums and the own row
 template <typename T>
 __global__ __launch_bounds__(kThreads) void nmh_player_features_kernel(
     const T* __restrict__ ents, int64_t ent_stride, int R, const void* __restrict__ ids, int64_t id_stride,
     int id_kind, float* __restrict__ features, float* __restrict__ sums, float* __restrict__ mine,
     int32_t* __restrict__ mine_idx) {
-  constexpr int kU = 4;
   __shared__ float s_part[kSlots][kC];
   __shared__ int s_cnt[kTypes];
   __shared__ int s_first;
@@ -83,29 +83,11 @@ __global__ __launch_bounds__(kThreads) void nmh_player_features_kernel(
   const T* __restrict__ set = ents + m * ent_stride;
   float* __restrict__ fset = features ? features + m * (int64_t)R * kF : nullptr;
   const float id = own ? load_id(ids, m * id_stride, id_kind) : 0.0f;
-  if (slot < kSlots) {
-    float acc = 0.0f;
-    for (int j0 = 0; j0 < R; j0 += kSlots * kU) {
-      T v[kU];
-#pragma unroll
-      for (int u = 0; u < kU; ++u) {
-        const int j = j0 + u * kSlots + slot;
-        v[u] = j < R ? set[(int64_t)j * kC + c] : (T)0;
-      }
-#pragma unroll
-      for (int u = 0; u < kU; ++u) {
-        const int j = j0 + u * kSlots + slot;
-        if (j < R) {
-          const float x = (float)v[u];
-          acc += x;
-          if (c == kTypeCol) atomicAdd(&s_cnt[npc_class(x)], 1);
-          if (c == 0 && own && x == id && x != 0.0f) atomicMin(&s_first, j);
-          if (fset) put_x(fset + (int64_t)j * kF, c, x);
-        }
-      }
-    }
-    s_part[slot][c] = acc;
-  }
+  if (slot < kSlots)
+    s_part[slot][c] = set_dev::scan_set<kC>(set, R, slot, c, own, id, &s_first, [&](int j, float x) {
+      if (c == kTypeCol) atomicAdd(&s_cnt[npc_class(x)], 1);
+      if (fset) put_x(fset + (int64_t)j * kF, c, x);
+    });
   __syncthreads();
   if (sums && tid < kF) {
     float s;
@@ -174,10 +156,10 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void nmh_player_logits_kernel(
   wave_sync();
   for (int i0 = 0; i0 < cnt; i0 += kChunk) {
     const int n = min(kChunk, cnt - i0);
-    stage_rows(set, list, i0, n, rows);
+    set_dev::stage_rows<kC, kC>(set, list, i0, n, rows);
     wave_sync();
     if (lane < n) {
-      const int entry = list[i0 + lane], j = entry & ((1 << kHeadShift) - 1), hm = entry >> kHeadShift;
+      const int entry = list[i0 + lane], j = entry & kJMask, hm = entry >> kHeadShift;
       const float* row = rows + lane * kC;
 #pragma unroll
       for (int h = 0; h < kMaxHeads; ++h)
@@ -209,9 +191,9 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void nmh_player_logits_backward
   wave_sync();
   for (int i0 = 0; i0 < cnt; i0 += kChunk) {
     const int n = min(kChunk, cnt - i0);
-    stage_rows(set, list, i0, n, rows);
+    set_dev::stage_rows<kC, kC>(set, list, i0, n, rows);
     if (f < n) {  // lane k: listed candidate k's g_out in the heads that allow it, no other entry
-      const int entry = list[i0 + f], j = entry & ((1 << kHeadShift) - 1), hm = entry >> kHeadShift;
+      const int entry = list[i0 + f], j = entry & kJMask, hm = entry >> kHeadShift;
 #pragma unroll
       for (int h = 0; h < kMaxHeads; ++h)
         if (h < H && (hm >> h & 1)) s_g[w][h][f] = grow[ph.out_off[h] + j];
@@ -247,16 +229,12 @@ int nmh_player_features(int32_t n_sets, const void* ents, int64_t ent_stride, in
                         float* mine, int32_t* mine_idx, void* stream) {
   const char* fn = "nmh_player_features";
   if (n_sets < 0) return heads_fail(NMH_E_INVALID, "%s: n_sets %d is negative", fn, n_sets);
-  const int rc = check_set(fn, kEntitySets, ents, ent_stride, ent_kind, set_rows);
+  int rc = check_set(fn, kEntitySets, ents, ent_stride, ent_kind, set_rows);
   if (rc != NMH_OK) return rc;
   if (!features && !sums && !mine && !mine_idx)
     return heads_fail(NMH_E_INVALID, "%s: features, sums, mine and mine_idx are all NULL", fn);
-  if (mine || mine_idx) {
-    if (!ids) return heads_fail(NMH_E_INVALID, "%s: ids is NULL but mine or mine_idx is not", fn);
-    if (id_kind != NMH_PLAYER_F32 && id_kind != NMH_PLAYER_I16)
-      return heads_fail(NMH_E_INVALID, "%s: unknown id_kind %d", fn, id_kind);
-    if (id_stride < 1) return heads_fail(NMH_E_INVALID, "%s: id_stride %lld < 1", fn, (long long)id_stride);
-  }
+  if (mine || mine_idx) rc = check_ids(fn, ids, id_stride, id_kind, "mine or mine_idx is");
+  if (rc != NMH_OK) return rc;
   if (n_sets == 0) return NMH_OK;
   const bool f32 = ent_kind == NMH_PLAYER_F32;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -285,12 +263,9 @@ int nmh_player_logits(const NmhPlayerHeads* ph, int32_t n_rows, const void* ents
                       int32_t ent_kind, int32_t set_rows, const void* mask, int64_t mask_stride, int32_t mask_kind,
                       const float* pq, float* out, int64_t out_stride, void* stream) {
   const char* fn = "nmh_player_logits";
-  const int rc = check_logits(fn, kEntitySets, ph, n_rows, ents, ent_stride, ent_kind, set_rows, 1, mask, mask_stride,
-                              mask_kind, "out", out, "out_stride", out_stride);
-  if (rc != NMH_OK) return rc;
-  if (!pq) return heads_fail(NMH_E_INVALID, "%s: pq is NULL", fn);
-  if (!aligned16(pq)) return heads_fail(NMH_E_INVALID, "%s: pq is not 16-byte aligned", fn);
-  if (n_rows == 0) return NMH_OK;
+  const int rc = check_forward(fn, kEntitySets, ph, n_rows, ents, ent_stride, ent_kind, set_rows, 1, mask, mask_stride,
+                               mask_kind, pq, out, out_stride);
+  if (rc != NMH_OK || n_rows == 0) return rc;
   HEADS_SET_LAUNCH(nmh_player_logits_kernel, ent_kind, mask_kind, kRowsPerBlock, stream, ph, n_rows, ents, ent_stride,
                    set_rows, mask, mask_stride, pq, out, out_stride);
   return heads_launched(fn);
@@ -300,11 +275,9 @@ int nmh_player_logits_backward(const NmhPlayerHeads* ph, int32_t n_rows, const v
                                int32_t ent_kind, int32_t set_rows, const void* mask, int64_t mask_stride,
                                int32_t mask_kind, const float* g_out, int64_t g_stride, float* g_pq, void* stream) {
   const char* fn = "nmh_player_logits_backward";
-  const int rc = check_logits(fn, kEntitySets, ph, n_rows, ents, ent_stride, ent_kind, set_rows, 1, mask, mask_stride,
-                              mask_kind, "g_out", g_out, "g_stride", g_stride);
-  if (rc != NMH_OK) return rc;
-  if (!g_pq) return heads_fail(NMH_E_INVALID, "%s: g_pq is NULL", fn);
-  if (n_rows == 0) return NMH_OK;
+  const int rc = check_backward(fn, kEntitySets, ph, n_rows, ents, ent_stride, ent_kind, set_rows, 1, mask,
+                                mask_stride, mask_kind, g_out, g_stride, g_pq);
+  if (rc != NMH_OK || n_rows == 0) return rc;
   HEADS_SET_LAUNCH(nmh_player_logits_backward_kernel, ent_kind, mask_kind, kRowsPerBlock, stream, ph, n_rows, ents,
                    ent_stride, set_rows, mask, mask_stride, g_out, g_stride, g_pq);
   return heads_launched(fn);

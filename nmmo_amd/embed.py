@@ -95,9 +95,7 @@ def own_row_ref(ents: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
     """The index [N] int64 of each row's own entity of ents [N, R, 31]: the first j whose column 0
     equals the row's id and is not 0, else 0 (SPEC §21's rule, the reference's lines 177-182)."""
     col = ents[..., ID_COL]
-    col = col if col.is_floating_point() else col.to(torch.float32)
-    match = (col == ids.reshape(-1, 1).to(col.dtype)) & (col != 0)
-    return torch.where(match.any(1), match.int().argmax(1), torch.zeros_like(match.sum(1)))
+    return _sets.own_row_index(col if col.is_floating_point() else col.to(torch.float32), ids)
 
 
 # ---------------------------------------------------------------- the kernels
@@ -106,11 +104,7 @@ def _call(kind: Kind, sets, ids, set_rows, want):
         raise HeadsError("embed_features / embed_counts / embed_own run on the GPU: sets and ids must be device tensors")
     x, stride, rows, ek = _sets.set_arg(sets.detach(), set_rows, kind.spec)
     m, dev = x.shape[0], x.device
-    idt, id_stride, id_kind = None, 1, _sets.ELEM_F32
-    if ids is not None:
-        from .player import _id_arg
-
-        idt, id_stride, id_kind = _id_arg(ids.detach(), m)
+    idt, id_stride, id_kind = (None, 1, _sets.ELEM_F32) if ids is None else _sets.id_arg(ids.detach(), m)
     D, C = kind.D, kind.C
 
     def new(name, shape, dtype=torch.float32):
@@ -187,14 +181,8 @@ class _EmbeddedEncoder(nn.Module):
     def _fc(self) -> nn.Linear:
         return getattr(self, self.layer)
 
-    def _rows(self, sets: torch.Tensor, set_rows) -> int:
-        return sets.shape[1] if sets.dim() == 3 else (sets.shape[1] // self.kind.cols if set_rows is None else int(set_rows))
-
     def _sets(self, sets: torch.Tensor, set_rows) -> torch.Tensor:
-        if sets.dim() == 3:
-            return sets
-        rows = self._rows(sets, set_rows)
-        return sets[:, :rows * self.kind.cols].reshape(sets.shape[0], rows, self.kind.cols)
+        return _sets.as_sets(sets, set_rows, self.kind.cols)
 
     def _feat(self, idx: torch.Tensor, cont: torch.Tensor) -> torch.Tensor:
         """cat(E[idx], cont) [..., 32 D + C]: the reference's lines 191-198."""
@@ -213,7 +201,7 @@ class _EmbeddedEncoder(nn.Module):
         """mean_j fc(feat_j) [M, H]. Fused: fc of the mean feature, from the bin counts and column sums."""
         if not self.fused:
             return self.embed(sets, set_rows).mean(1)
-        k, rows = self.kind, self._rows(sets, set_rows)
+        k, rows = self.kind, _sets.set_rows_of(sets, set_rows, self.kind.cols)
         counts, sums = embed_counts(k, sets, set_rows=set_rows)
         mean_e = (counts @ self.embedding.weight[:BINS]).flatten(-2) / rows
         mean_c = sums / torch.tensor(k.cdivs, dtype=sums.dtype, device=sums.device) / rows

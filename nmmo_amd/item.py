@@ -123,17 +123,10 @@ class ItemEncoder(nn.Module):
         self.fused = bool(fused)
         self.fc = nn.Linear(FEATURES, hidden)
 
-    @staticmethod
-    def _sets(items: torch.Tensor, set_rows):
-        if items.dim() == 3:
-            return items
-        rows = items.shape[1] // COLS if set_rows is None else int(set_rows)
-        return items[:, :rows * COLS].reshape(items.shape[0], rows, COLS)
-
     def features(self, items: torch.Tensor, set_rows=None) -> torch.Tensor:
         if self.fused:
             return item_features(items, set_rows=set_rows)
-        return item_features_ref(self._sets(items, set_rows)).to(self.fc.weight.dtype)
+        return item_features_ref(_sets.as_sets(items, set_rows, COLS)).to(self.fc.weight.dtype)
 
     def embed(self, items: torch.Tensor, set_rows=None) -> torch.Tensor:
         """fc(x) [M, R, H]: the reference's forward."""
@@ -142,7 +135,7 @@ class ItemEncoder(nn.Module):
     def pooled(self, items: torch.Tensor, set_rows=None) -> torch.Tensor:
         """mean_j fc(x_j) [M, H]. Fused: fc(sum_j x_j / R), without the [M, R, .] tensors."""
         if self.fused:
-            rows = items.shape[1] if items.dim() == 3 else (items.shape[1] // COLS if set_rows is None else set_rows)
+            rows = _sets.set_rows_of(items, set_rows, COLS)
             return F.linear(item_sums(items, set_rows=set_rows) / rows, self.fc.weight, self.fc.bias)
         return self.embed(items, set_rows).mean(1)
 

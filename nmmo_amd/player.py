@@ -40,7 +40,7 @@ ID_COL, TYPE_COL = 0, 1
 SPEC = _sets.SetSpec("player_logits", "nmh_player_logits", "ents", "N", "entities", "entity", COLS, QUERY, MAX_ROWS,
                      share=False)
 NmhPlayerHeads = _sets.NmhSetHeads
-_kind, _ptr = _sets.elem_kind, heads.ptr
+_ptr = heads.ptr
 
 
 def player_heads_struct(mask_off, out_off) -> NmhPlayerHeads:
@@ -62,9 +62,7 @@ def own_row_ref(ents: torch.Tensor, ids: torch.Tensor):
     AgentId [N] in plain torch: the first j whose column 0 equals the id and is not 0, else 0 (the
     reference's lines 132-140). A NaN id matches nothing."""
     feats = player_features_ref(ents)
-    col = feats[..., ID_COL]
-    match = (col == ids.reshape(-1, 1).to(col.dtype)) & (col != 0)
-    idx = torch.where(match.any(1), match.int().argmax(1), torch.zeros_like(match.sum(1)))
+    idx = _sets.own_row_index(feats[..., ID_COL], ids)
     return feats[torch.arange(feats.shape[0], device=feats.device), idx], idx
 
 
@@ -73,17 +71,7 @@ def _ent_arg(x: torch.Tensor, set_rows):
     return _sets.set_arg(x, set_rows, SPEC)
 
 
-def _id_arg(ids: torch.Tensor, n: int):
-    """(tensor kept alive, element stride, NMH_PLAYER_*) of the rows' AgentId read in place: [N] or
-    [N, 1], any positive stride (a column of the obs rows)."""
-    if ids.dim() == 2 and ids.shape[1] == 1:
-        ids = ids[:, 0]
-    if ids.dim() != 1 or ids.shape[0] != n:
-        raise ValueError(f"ids must be [{n}] or [{n}, 1], got {tuple(ids.shape)}")
-    kind = _kind(ids, "ids")
-    if n > 1 and ids.stride(0) < 1:
-        ids = ids.contiguous()
-    return ids, max(ids.stride(0), 1), kind
+_id_arg = _sets.id_arg
 
 
 def _features(ents, ids, set_rows, want: str):
@@ -161,21 +149,10 @@ class PlayerEncoder(nn.Module):
         self.agent_fc = nn.Linear(FEATURES, hidden_size)
         self.my_agent_fc = nn.Linear(FEATURES, input_size)
 
-    @staticmethod
-    def _rows(ents: torch.Tensor, set_rows) -> int:
-        return ents.shape[1] if ents.dim() == 3 else (ents.shape[1] // COLS if set_rows is None else int(set_rows))
-
-    @classmethod
-    def _sets(cls, ents: torch.Tensor, set_rows):
-        if ents.dim() == 3:
-            return ents
-        rows = cls._rows(ents, set_rows)
-        return ents[:, :rows * COLS].reshape(ents.shape[0], rows, COLS)
-
     def features(self, ents: torch.Tensor, set_rows=None) -> torch.Tensor:
         if self.fused:
             return player_features(ents, set_rows=set_rows)
-        return player_features_ref(self._sets(ents, set_rows)).to(self.agent_fc.weight.dtype)
+        return player_features_ref(_sets.as_sets(ents, set_rows, COLS)).to(self.agent_fc.weight.dtype)
 
     def embed(self, ents: torch.Tensor, set_rows=None) -> torch.Tensor:
         """agent_fc(x) [N, R, H]: the reference's agent_embeddings."""
@@ -185,7 +162,7 @@ class PlayerEncoder(nn.Module):
         """mean_j agent_fc(x_j) [N, H]. Fused: agent_fc(sum_j x_j / R), without the [N, R, .] tensors."""
         if self.fused:
             sums = player_sums(ents, set_rows=set_rows)
-            return F.linear(sums / self._rows(ents, set_rows), self.agent_fc.weight, self.agent_fc.bias)
+            return F.linear(sums / _sets.set_rows_of(ents, set_rows, COLS), self.agent_fc.weight, self.agent_fc.bias)
         return self.embed(ents, set_rows).mean(1)
 
     def my_agent(self, ents: torch.Tensor, ids: torch.Tensor, set_rows=None) -> torch.Tensor:
@@ -193,7 +170,7 @@ class PlayerEncoder(nn.Module):
         if self.fused:
             mine = player_own(ents, ids, set_rows=set_rows)[0]
         else:
-            mine = own_row_ref(self._sets(ents, set_rows), ids)[0].to(self.my_agent_fc.weight.dtype)
+            mine = own_row_ref(_sets.as_sets(ents, set_rows, COLS), ids)[0].to(self.my_agent_fc.weight.dtype)
         return F.relu(self.my_agent_fc(mine))
 
     def pointer_query(self, q: torch.Tensor) -> torch.Tensor:
